@@ -2,16 +2,21 @@
 Benchmark of the IMEX hot path: timesteps/sec of 3-D Rayleigh-Benard (Fourier x Fourier x Chebyshev,
 RK222, fixed dt) -- BASELINE.json's metric.
 
-    python bench.py --gpus N --steps K --warmup W [--size NX,NY,NZ]
+    python bench.py --gpus N --steps K --warmup W [--size NX,NY,NZ] [--dump-outputs DIR] [--full]
 
 N=1 runs the largest configuration that fits one MI355X (the metric's 512x512x256 by default).
 For N>1 the pencils are sharded across N ranks, one per GPU, exchanging through RCCL (the metric's problem size is
 fixed, so this is "strong" scaling: total work constant).  `python bench.py --gpus N` launches the N ranks itself
-(re-executing under torch.distributed.run on 127.0.0.1) when it was not already started by a launcher.
+(starting a child process under torch.distributed.run on 127.0.0.1) when it was not already started by a launcher.
 
-Rank 0 prints ONE JSON line with the timing, the roofline of the dominant kernel (algorithmic bytes
-per launch / HIP-event time, measured inside the timed region) and a CPU baseline (the numpy/scipy
-oracle executor -- the reference's per-pencil algorithm -- on a bounded sample).
+A plain run sets up the problem, runs W warm-up steps, times exactly K steps once and prints ONE JSON line on rank 0
+(`value` = timesteps/sec, `ms_per_step`).  `--dump-outputs DIR` writes the state the last timed step left behind as
+DIR/<field>.npy (float64 coefficients; a fixed, seeded sample of the larger fields, see dump_outputs()).
+
+`--full` adds everything else to the line: the K steps repeated `--repeats` times with every kernel family timed by HIP
+events (the roofline of the dominant kernel: algorithmic bytes per launch / HIP-event time), the end-state checksum,
+the pencil parity probe, the adaptive-timestep mode (`cfl_mode`), the exchange paths of a sharded run and a CPU
+baseline (the numpy/scipy oracle executor -- the reference's per-pencil algorithm -- on bounded samples).
 """
 
 import argparse
@@ -80,12 +85,19 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=10)     # (the reference's warmup_iterations, core/solvers.py:546)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure, measure and check everything else: per-kernel HIP-event timing "
+                         "and roofline, repeats, checksum, pencil parity, cfl_mode, exchange paths, CPU baseline")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write the state the last timed step computed as DIR/<field>.npy "
+                         "(float64; at most 64 MB in all)")
     ap.add_argument("--repeats", type=int, default=3,
-                    help="the K timed steps are repeated this many times back to back (each repeat bracketed by its own "
-                         "barrier + synchronize); the line reports the MEDIAN repeat and lists all of them")
+                    help="(--full) the K timed steps are repeated this many times back to back (each repeat bracketed by "
+                         "its own barrier + synchronize); the line reports the MEDIAN repeat and lists all of them.  "
+                         "A plain run times the K steps once")
     ap.add_argument("--size", type=str, default=os.environ.get("BENCH_SIZE", "512,512,256"))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-parity", action="store_true", help="(--full) skip the pencil parity probe")
     ap.add_argument("--cpu-budget", type=float, default=120.0,
                     help="budget of the one-core cpu_baseline samples; >= 100 (default 120) includes 128x128x64, the sample the value "
                          "extrapolates from (~1 min of setup + ~7 s per step)")
@@ -97,7 +109,7 @@ def parse():
     ap.add_argument("--dt", type=float, default=1e-3)
     ap.add_argument("--cfl", action="store_true", help="(kept for old command lines: the adaptive loop now runs by default)")
     ap.add_argument("--no-cfl", action="store_true",
-                    help="skip the second reported mode: after the fixed-dt measurement (the metric) the example's adaptive "
+                    help="(--full) skip the second reported mode: after the fixed-dt measurement (the metric) the example's adaptive "
                          "loop -- d3.CFL(cadence=10, threshold=0.05) on an O(1) flow, i.e. with LHS refactorizations -- is "
                          "timed and reported as `cfl_mode` beside the fixed-dt value (one GPU only)")
     ap.add_argument("--cfl-steps", type=int, default=40)
@@ -108,8 +120,10 @@ def parse():
 
 
 def launch_ranks(n):
-    """`python bench.py --gpus N` without a launcher: become `torch.distributed.run --nproc-per-node N bench.py ...`."""
+    """`python bench.py --gpus N` without a launcher: run `torch.distributed.run --nproc-per-node N bench.py ...` as a
+    child process and exit with its status."""
     import socket
+    import subprocess
     with socket.socket() as sock:
         sock.bind(("127.0.0.1", 0))
         port = sock.getsockname()[1]
@@ -120,7 +134,7 @@ def launch_ranks(n):
     if os.environ.get("BENCH_DRY_LAUNCH"):          # (tests: show the launch line instead of running it)
         print(json.dumps(cmd))
         sys.exit(0)
-    os.execvpe(cmd[0], cmd, env)
+    sys.exit(subprocess.call(cmd, env=env))
 
 
 def host_info():
@@ -343,16 +357,40 @@ def adaptive_loop(d3, solver, fields, args, torch):
                      "timestep change refactors all pencils (factor kernel + device inversion of the mean-mode pencil)")
 
 
+DUMP_SAMPLE = 1 << 20           # values kept of a field with more coefficients than this (8 MB in float64)
+
+
+def dump_outputs(fields, out_dir):
+    """What a caller of the timed path receives after its last step: the coefficients of every state field, written as
+    out_dir/<name>.npy in float64, flattened in C order.  A field of more than DUMP_SAMPLE values is sampled at
+    DUMP_SAMPLE distinct flat indices drawn by numpy.random.default_rng(0).choice(size, DUMP_SAMPLE, replace=False)
+    and sorted: the same indices for the same field shape, so that two builds compare value for value.  The seven
+    fields of the 3-D problem stay under 64 MB in all at any size."""
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name in sorted(fields):
+        a = np.asarray(fields[name]["c"], dtype=np.float64).ravel()
+        if a.size > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))
+            a = a[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+        written[name] = int(a.size)
+    return written
+
+
 def main():
     args = parse()
     if args.cpu_worker:                          # one replica of cpu_replicas(): no GPU, no torch
         print(json.dumps(cpu_sample(args.cpu_worker, args.cpu_worker_seconds, args.cpu_worker_which)))
         return
     if args.emulate_rank:                        # one rank of a sharded run on one GPU: its own tool, its own output
+        import subprocess
         r, P = args.emulate_rank.split("/")
         cmd = [sys.executable, os.path.join(ROOT, "tools", "rank_emulation.py"), "--ranks", P, "--rank", r, "--size", args.size,
                "--steps", str(args.steps), "--warmup", str(min(args.warmup, 5)), "--dt", str(args.dt)]
-        os.execv(cmd[0], cmd)
+        sys.exit(subprocess.call(cmd))
+    if args.dump_outputs and max(args.gpus, int(os.environ.get("WORLD_SIZE", "1"))) > 1:
+        sys.exit("bench.py: --dump-outputs writes the state of a one-GPU run (--gpus 1)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         launch_ranks(args.gpus)                   # does not return
     import torch
@@ -388,13 +426,14 @@ def main():
     ex.sync()
     if world > 1:
         torch.distributed.barrier()
-    timer = KernelTimer(torch)
+    full = args.full
+    timer = KernelTimer(torch) if full else None        # (--full: HIP events around every kernel family)
     ex.timer = timer
-    if world > 1:
+    if world > 1 and full:
         solver.dist.pcomm.via = {}
         solver.dist.pcomm.wire_events = []
     els = []
-    for _ in range(max(1, args.repeats)):               # every repeat: exactly K steps between barrier + synchronize
+    for _ in range(max(1, args.repeats) if full else 1):   # every repeat: exactly K steps between barrier + synchronize
         torch.cuda.synchronize()
         if world > 1:
             torch.distributed.barrier()
@@ -411,17 +450,40 @@ def main():
             e = float(t.item())
         els.append(e)
     ex.timer = None
-    if world > 1:
+    if world > 1 and full:
         wire_events = solver.dist.pcomm.wire_events            # (later steps -- parity probe -- add no events)
         solver.dist.pcomm.wire_events = None
         via_counts = {k: list(v) for k, v in solver.dist.pcomm.via.items()}
+    if args.dump_outputs:
+        dump_outputs(fields, args.dump_outputs)
     el = float(np.median(els))
     nrep = len(els)
-    summ = timer.summary()
     ranks_seen, backend, exch = 1, None, None
     if world > 1:
         ranks_seen = torch.distributed.get_world_size()
         backend = torch.distributed.get_backend()
+    out = {
+        "metric": "timesteps/sec, 3D Rayleigh-Benard %dx%dx%d (Fourier x Fourier x Chebyshev, RK222)" % (Nx, Ny, Nz),
+        "value": args.steps / el, "unit": "timesteps/sec", "n_gpus": ranks_seen, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": 1e3 * el / args.steps, "higher_is_better": True,
+        "repeats": {"n": nrep, "steps_per_s": [args.steps / e for e in els], "reported": "median"},
+        "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": "3-D Rayleigh-Benard IVP %dx%dx%d, dealias 3/2, RK222, fixed dt=%g, Ra=2e6 Pr=1, "
+                               "example-script initial condition (fill_random seed 42)" % (Nx, Ny, Nz, args.dt),
+                   "pencils": (Nx // 2) * (Ny // 2), "rows_per_pencil_real": 4 * solver.R,
+                   "layouts": {"state_vector": "tile-major" if getattr(solver, "x_tiled", 0) else "natural",
+                               "right_hand_sides": "tile-major" if getattr(solver.timestepper, "_tiled", 0) else "natural"},
+                   "parallelism": "1 GPU" if world == 1 else "%d GPUs, pencils sharded on kx, RCCL all-to-all" % world},
+        "build_s": build_s, "ranks_seen": ranks_seen, "dist_backend": backend,
+    }
+    if not full:                                 # a plain run: the headline figure and nothing else
+        if rank == 0:
+            print(json.dumps(out))
+        if world > 1:
+            torch.distributed.destroy_process_group()
+        return
+    summ = timer.summary()
+    if world > 1:
         pc = solver.dist.pcomm
         nst = args.steps * nrep                       # (the per-path counters were reset after the warm-up)
         # the code path every exchange of the timed steps really took (parallel.Comm.via), not what could have been used
@@ -470,7 +532,6 @@ def main():
     cfl_mode = adaptive_loop(d3, solver, fields, args, torch) if (not args.no_cfl and world == 1) else None
 
     if rank == 0:
-        steps_per_s = args.steps / el
         # dominant kernel family by total time
         comp = {k: v for k, v in summ.items() if k != "a2a_exchange"}      # (the exchange is reported separately)
         dom = max(comp.items(), key=lambda kv: kv[1]["total_ms"]) if comp else (None, None)
@@ -500,27 +561,15 @@ def main():
                                   "assume 2.4 GHz")
         total_kernel_ms = sum(v["total_ms"] for v in summ.values())
         total_bytes = sum(v["bytes_per_launch"] * v["launches"] for v in summ.values())
-        out = {
-            "metric": "timesteps/sec, 3D Rayleigh-Benard %dx%dx%d (Fourier x Fourier x Chebyshev, RK222)" % (Nx, Ny, Nz),
-            "value": steps_per_s, "unit": "timesteps/sec", "n_gpus": ranks_seen, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": 1e3 * el / args.steps, "higher_is_better": True,
-            "repeats": {"n": nrep, "steps_per_s": [args.steps / e for e in els], "reported": "median"},
-            "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": "3-D Rayleigh-Benard IVP %dx%dx%d, dealias 3/2, RK222, fixed dt=%g, Ra=2e6 Pr=1, "
-                                   "example-script initial condition (fill_random seed 42)" % (Nx, Ny, Nz, args.dt),
-                       "pencils": (Nx // 2) * (Ny // 2), "rows_per_pencil_real": 4 * solver.R,
-                       "layouts": {"state_vector": "tile-major" if getattr(solver, "x_tiled", 0) else "natural",
-                                   "right_hand_sides": "tile-major" if getattr(solver.timestepper, "_tiled", 0) else "natural"},
-                       "parallelism": "1 GPU" if world == 1 else "%d GPUs, pencils sharded on kx, RCCL all-to-all" % world},
+        out.update({
             "roofline": roof,
             "whole_step": {"algorithmic_GB_per_step": total_bytes / (args.steps * nrep) / 1e9,
                            "kernel_ms_per_step": total_kernel_ms / (args.steps * nrep),
                            "achieved_GBps_all_kernels": (total_bytes / 1e9) / (total_kernel_ms / 1e3) if total_kernel_ms else None},
             "kernels": {k: {"launches": v["launches"], "avg_ms": round(v["avg_ms"], 4), "GBps": round(v["gbps"], 1),
                             "total_ms": round(v["total_ms"], 2)} for k, v in sorted(summ.items())},
-            "build_s": build_s, "checksum_b_c_l2": chk, "parity": parity,
-            "ranks_seen": ranks_seen, "dist_backend": backend, "exchange": exch,
-        }
+            "checksum_b_c_l2": chk, "parity": parity, "exchange": exch,
+        })
         if cfl_mode is not None:
             out["cfl_mode"] = cfl_mode
         if not args.no_cpu_baseline and world == 1:          # rank 0 at N = 1 only

@@ -132,7 +132,7 @@ def test_two_rank_nccl_bench_at_full_size_matches_the_one_gpu_run():
     lines = {}
     for n in (1, 2):
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1",
-               "--no-cpu-baseline"]
+               "--full", "--no-cpu-baseline"]
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, env=env)
         assert r.returncode == 0, r.stderr[-3000:]
         lines[n] = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -193,7 +193,7 @@ def test_two_rank_bench_line_names_the_exchange_paths_taken():
     import json
     env = dict(os.environ, OMP_NUM_THREADS="1", DDH_DIST_BACKEND="gloo", DDH_FORCE_DEVICE="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--size", "32,32,16", "--steps", "2", "--warmup", "1",
-           "--repeats", "1", "--no-cpu-baseline"]
+           "--full", "--repeats", "1", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

@@ -22,10 +22,10 @@ for step in "$@"; do
     tests)      python -m pytest tests -x -q -m gpu > $OUT/pytest.txt 2>&1; tail -3 $OUT/pytest.txt ;;
     tests-solve) python -m pytest tests/test_gpu_pencil.py tests/test_gpu_reference_pencils.py tests/test_gpu_ivp.py -x -q -m gpu > $OUT/pytest_solve.txt 2>&1; tail -5 $OUT/pytest_solve.txt ;;
     smoke)      python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 ;;
-    bench)      python bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; bench_line $OUT/bench.json ;;
-    bench-quick) python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_quick.json 2> $OUT/bench_quick.err; bench_line $OUT/bench_quick.json ;;
-    bench-nosplit) DDH_NO_SPLIT=1 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_nosplit.json 2> $OUT/bench_nosplit.err; bench_line $OUT/bench_nosplit.json ;;
-    bench-cfl)  python bench.py --steps 10 --warmup 3 --cfl --no-cpu-baseline > $OUT/bench_cfl.json 2> $OUT/bench_cfl.err; bench_line $OUT/bench_cfl.json ;;
+    bench)      python bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; bench_line $OUT/bench.json ;;
+    bench-quick) python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_quick.json 2> $OUT/bench_quick.err; bench_line $OUT/bench_quick.json ;;
+    bench-nosplit) DDH_NO_SPLIT=1 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_nosplit.json 2> $OUT/bench_nosplit.err; bench_line $OUT/bench_nosplit.json ;;
+    bench-cfl)  python bench.py --full --steps 10 --warmup 3 --cfl --no-cpu-baseline > $OUT/bench_cfl.json 2> $OUT/bench_cfl.err; bench_line $OUT/bench_cfl.json ;;
     profile)    timeout 900 bash tools/profile_round.sh $TAG > $OUT/profile.log 2>&1; tail -3 $OUT/profile.log ;;
     ellband)    # shell LHS at config H: band LU against the dense inverses (solve / factorization device time, per-kernel table)
                 export TMPDIR=/tmp
@@ -46,7 +46,7 @@ for step in "$@"; do
                 DDH_BLOCK_INVERSE=0 python tools/bench_configs.py r2 2>&1 | grep -v "^\[" | head -2 | tee -a $OUT/r2.txt ;;
     shell-sweep) for envs in "X=0" "DDH_FFT_B=4" "DDH_FFT_B=8" "DDH_FFT_B=16" "DDH_FFT_OCC4=1" "DDH_FFT_B=8 DDH_FFT_OCC4=1"; do echo "$envs" | tee -a $OUT/shell_sweep.txt; env $envs python tools/bench_configs.py shell 2>&1 | grep "steps/s" | head -1 | tee -a $OUT/shell_sweep.txt; done ;;
     tests-fused) python -m pytest tests/test_gpu_wave_transforms.py tests/test_gpu_transforms.py -x -q -m gpu -k "fused" > $OUT/pytest_fused.txt 2>&1; tail -3 $OUT/pytest_fused.txt ;;
-    bench-v1)   DDH_GW_V2=0 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-cfl > $OUT/bench_v1.json 2> $OUT/bench_v1.err; bench_line $OUT/bench_v1.json ;;
+    bench-v1)   DDH_GW_V2=0 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-cfl > $OUT/bench_v1.json 2> $OUT/bench_v1.err; bench_line $OUT/bench_v1.json ;;
     sphere)     python -m pytest tests/test_gpu_swsh.py tests/test_gpu_sphere.py tests/test_gpu_shell.py -x -q -m gpu > $OUT/pytest_sphere.txt 2>&1; tail -3 $OUT/pytest_sphere.txt
                 python tools/bench_configs.py sphere 2>&1 | grep -v "^\[" | tail -3 | tee -a $OUT/sphere.txt ;;
     configs)    python tools/bench_configs.py --json > $OUT/configs.json 2> $OUT/configs.err; tail -5 $OUT/configs.json ;;
@@ -55,7 +55,7 @@ for step in "$@"; do
                 for sz in 256,512,256 128,512,256 64,512,256; do
                   for var in "default:" "per-thread:DDH_SOLVE_COOP=0" "per-thread-unsplit:DDH_SOLVE_COOP=0 DDH_SPLIT_THREADS=0" "coop-fwd+cb4:DDH_COOP_FWD=1 DDH_COOP_CB=4" "cb4:DDH_COOP_FWD=0 DDH_COOP_CB=4"; do
                     name=${var%%:*}; envs=${var#*:}
-                    env $envs python bench.py --size $sz --steps 10 --warmup 3 --repeats 1 --no-cpu-baseline --no-parity --no-cfl > $OUT/share_${sz//,/x}_$name.json 2>/dev/null
+                    env $envs python bench.py --full --size $sz --steps 10 --warmup 3 --repeats 1 --no-cpu-baseline --no-parity --no-cfl > $OUT/share_${sz//,/x}_$name.json 2>/dev/null
                     python - $OUT/share_${sz//,/x}_$name.json "$sz $name" <<'PY'
 import json, sys
 try:
@@ -70,7 +70,7 @@ PY
                 done ;;
     ring-ab)    # backward sweep: direct loads against the LDS-DMA ring, depth 2 / 3 / 4 (DDH_BWD_RING), same box
                 for r in 0 2 3 4; do
-                  DDH_BWD_RING=$r python bench.py --steps 10 --warmup 3 --repeats 1 --no-cpu-baseline --no-cfl > $OUT/bench_ring$r.json 2> $OUT/bench_ring$r.err
+                  DDH_BWD_RING=$r python bench.py --full --steps 10 --warmup 3 --repeats 1 --no-cpu-baseline --no-cfl > $OUT/bench_ring$r.json 2> $OUT/bench_ring$r.err
                   echo "DDH_BWD_RING=$r"; bench_line $OUT/bench_ring$r.json
                 done ;;
     emu)        # one rank of the P-rank run on this GPU, loop-back exchange (profiles/r6_rank_emulation.txt)
@@ -88,7 +88,7 @@ PY
                   echo "P=$P $v"; env $v python tools/rank_emulation.py --ranks $P --rank 1 --steps 10 --warmup 8 --link-gbps 75 2>&1 >/dev/null | cut -c1-120; done; done 2>&1 | tee $OUT/emu_defer_ab.txt ;;
     xtiled)     # tile-major state vector: bench A/B with the parity probe, then the suites that step problems with it forced on
                 python tools/gpu/xtile_diag.py
-                for v in "0" "1" "2" "0" "1" "2"; do env DDH_X_TILED=$v python bench.py --steps 10 --warmup 3 --repeats 1 --no-cpu-baseline --no-cfl > $OUT/bench_xtiled.json 2> $OUT/bench_xtiled.err
+                for v in "0" "1" "2" "0" "1" "2"; do env DDH_X_TILED=$v python bench.py --full --steps 10 --warmup 3 --repeats 1 --no-cpu-baseline --no-cfl > $OUT/bench_xtiled.json 2> $OUT/bench_xtiled.err
                   echo "DDH_X_TILED=$v"; bench_line $OUT/bench_xtiled.json | cut -c1-400
                   python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print('   parity', {k: d['parity'][k] for k in ('max_residual', 'max_solution_error')})" $OUT/bench_xtiled.json
                 done
@@ -98,19 +98,19 @@ PY
                 for P in 8 4; do for v in 1 2 4; do
                   echo "P=$P DDH_A2A_WINDOWS=$v"; env DDH_A2A_WINDOWS=$v python tools/rank_emulation.py --ranks $P --rank 1 --steps 10 --warmup 8 --link-gbps 75 2>&1 >/dev/null | cut -c1-220; done; done 2>&1 | tee $OUT/emu_windows_ab.txt ;;
     bwd-rowmajor) # timing experiment: the backward sweep reading the factor rows as if stored row-major over the blocks
-                for v in 0 128; do DDH_BWD_DBG=$v python bench.py --steps 10 --warmup 3 --repeats 1 --no-cpu-baseline --no-cfl --no-parity > $OUT/bench_bwddbg$v.json 2> $OUT/bench_bwddbg$v.err
+                for v in 0 128; do DDH_BWD_DBG=$v python bench.py --full --steps 10 --warmup 3 --repeats 1 --no-cpu-baseline --no-cfl --no-parity > $OUT/bench_bwddbg$v.json 2> $OUT/bench_bwddbg$v.err
                   echo "DDH_BWD_DBG=$v"; bench_line $OUT/bench_bwddbg$v.json; done ;;
     deep-ab)    # few-system sweeps: deep register prefetch (solve_*_deep_kernel) against the plain kernels, bit identity + time
                 for sz in 64,512,256 128,512,256; do for v in 0 1 "1 DDH_BWD_DEEP_PD=4"; do
-                  env DDH_SWEEP_DEEP=$v python bench.py --size $sz --steps 10 --warmup 3 --repeats 1 --no-cpu-baseline --no-cfl --no-parity > $OUT/bench_deep.json 2> $OUT/bench_deep.err
+                  env DDH_SWEEP_DEEP=$v python bench.py --full --size $sz --steps 10 --warmup 3 --repeats 1 --no-cpu-baseline --no-cfl --no-parity > $OUT/bench_deep.json 2> $OUT/bench_deep.err
                   echo "size $sz DDH_SWEEP_DEEP=$v"; bench_line $OUT/bench_deep.json; done; done
                 DDH_SWEEP_DEEP=1 python -m pytest tests/test_gpu_pencil.py tests/test_gpu_reference_pencils.py -x -q -m gpu > $OUT/pytest_deep.txt 2>&1; tail -3 $OUT/pytest_deep.txt ;;
     deep-big)   # the deep sweeps beyond their default range: 2 and 4 waves per SIMD worth of threads
                 for sz in 256,512,256 512,512,256; do for v in 0 1 "1 DDH_BWD_DEEP_PD=4"; do
-                  env DDH_SWEEP_DEEP=$v python bench.py --size $sz --steps 10 --warmup 3 --repeats 1 --no-cpu-baseline --no-cfl --no-parity > $OUT/bench_deep.json 2> $OUT/bench_deep.err
+                  env DDH_SWEEP_DEEP=$v python bench.py --full --size $sz --steps 10 --warmup 3 --repeats 1 --no-cpu-baseline --no-cfl --no-parity > $OUT/bench_deep.json 2> $OUT/bench_deep.err
                   echo "size $sz DDH_SWEEP_DEEP=$v"; bench_line $OUT/bench_deep.json; done; done ;;
     rowfill-ab) # backward sweep: entry pairs beyond the measured fill of a U row not loaded (LuDev::wrow), against all pairs
-                for v in 0 1 0 1; do DDH_BWD_ROW_FILL=$v python bench.py --steps 10 --warmup 3 --repeats 1 --no-cpu-baseline --no-cfl > $OUT/bench_rowfill$v.json 2> $OUT/bench_rowfill$v.err
+                for v in 0 1 0 1; do DDH_BWD_ROW_FILL=$v python bench.py --full --steps 10 --warmup 3 --repeats 1 --no-cpu-baseline --no-cfl > $OUT/bench_rowfill$v.json 2> $OUT/bench_rowfill$v.err
                   echo "DDH_BWD_ROW_FILL=$v"; bench_line $OUT/bench_rowfill$v.json; done ;;
     emu-block)  # the deep sweeps' workgroup size at the P = 4 / 8 shares
                 for b in 256 128 64; do echo "DDH_DEEP_BLOCK=$b"; DDH_DEEP_BLOCK=$b python tools/rank_emulation.py --ranks 4,8 --rank 1 --steps 10 --warmup 3 2>&1 >/dev/null | cut -c1-150; done ;;

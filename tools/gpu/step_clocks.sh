@@ -2,7 +2,7 @@
 # average of the management firmware over its own window)
 OUT=${GRAFT_REPO_ROOT:-$PWD}/gpurun_out/r5_step_clocks.txt
 : > $OUT
-python bench.py --steps 400 --warmup 5 --no-cpu-baseline > gpurun_out/r5_step_clocks_bench.json 2> gpurun_out/r5_step_clocks_bench.err &
+python bench.py --full --steps 400 --warmup 5 --no-cpu-baseline > ${OUT%.txt}_bench.json 2> ${OUT%.txt}_bench.err &
 PID=$!
 sleep 22
 for i in $(seq 1 12); do
@@ -11,9 +11,9 @@ for i in $(seq 1 12); do
   sleep 0.7
 done
 wait $PID
-python - <<'PY' >> $OUT
-import json
-d=json.loads(open("gpurun_out/r5_step_clocks_bench.json").read().strip().splitlines()[-1])
+python - ${OUT%.txt}_bench.json <<'PY' >> $OUT
+import json, sys
+d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 print("bench: steps/s %.3f ms %.2f"%(d["value"],d["ms_per_step"]))
 PY
 cat $OUT

@@ -9,7 +9,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $ROOT/bench.py --no-cpu-baseline"
+BENCH="python $ROOT/bench.py --full --no-cpu-baseline"
 # 1. kernel trace + stats over the default-length run (same command line as the committed bench JSON)
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- $BENCH --steps 5 --warmup 2 > $OUT/bench_stats_run.json 2> $OUT/stats.err
 # 2..4. PMC passes on a short run (1 warm-up + 1 timed step)
