@@ -173,9 +173,8 @@ struct PencilPack : HandleBase {
     std::vector<PostSolve> posts;
     std::vector<void *> post_mem;
     // sweep variant of ddh_pencil_solve: mode 1 = by the number of systems, 0 = one thread per system, 2 = cooperative;
-    // fwd / cb >= 0 override the forward kernel (0 / 1) and the backward lanes per system (0, 4, 16).  Initialised
-    // once from DDH_SOLVE_COOP / DDH_COOP_FWD / DDH_COOP_CB when the pack is created (not per launch);
-    // ddh_pencil_set_solve_variant changes them.
+    // fwd / cb >= 0 override the forward kernel (0 / 1) and the backward lanes per system (0, 4, 16).  Set by
+    // ddh_pencil_set_solve_variant; read by sweep_plan.
     int coop_mode = 1, coop_fwd = -1, coop_cb = -1;
     // x <-> y symmetry of the problem (ddh_pencil_set_pairing): physical row / column involutions, used by factorizations
     // of at least pair_min systems
@@ -387,14 +386,6 @@ __device__ __forceinline__ SysId sys_id(const PencilDev &P, const LuDev &L, long
         id.gl = REAL ? id.cell : g;
     }
     return id;
-}
-
-// wave-uniform: every lane of the wave works and the four lanes of each quad share one stored factorization -- the waves
-// solve_backward_ring_kernel takes; the others (unpaired cells of the axes and the diagonal, a ragged last wave) are left
-// to solve_backward_kernel<..., DBG = 64>
-__device__ __forceinline__ bool ring_wave(const SysId &id, int lane) {
-    const long gl_q = __shfl(id.gl, lane & ~3);
-    return __builtin_amdgcn_readfirstlane((int)(__ballot(id.ok && gl_q == id.gl) == ~0ull)) != 0;
 }
 
 // real factor of a term for the +kx system; the -kx system multiplies by (-1)^ex
@@ -739,9 +730,6 @@ struct RhsSrc {
     const unsigned char *zrow;   // optional, per row of the system vectors: 1 = the row is zero in EVERY term (not read)
     const unsigned char *skip;   // optional, per row of the solution: 1 = the caller does not need the row (not written)
     int tiled;                   // 1: the term vectors are stored tile-major (tile_offset), see ddh_pencil_solve_recombined_tiled
-#ifdef DDH_SWEEP_ABLATE
-    int abl;                     // timing ablations (results are NOT a solve): DDH_ABL bit mask, see launch_solve
-#endif
 };
 
 template <int NF, int XD = 1>
@@ -1691,19 +1679,6 @@ solve_forward_lean_kernel(PencilDev P, LuDev L, const RhsSrc rhs, double *__rest
 
     auto load_row = [&](int i) -> double2 {
         if (s_zero[i]) return make_double2(0.0, 0.0);           // wave-uniform
-#ifdef DDH_SWEEP_ABLATE
-        if (rhs.abl & 1) {                                      // right-hand-side terms from lane-contiguous addresses
-            double2 acc = make_double2(0.0, 0.0);
-#pragma unroll
-            for (int t = 0; t < RHS_MAX; ++t)
-                if (t < rhs.n) {
-                    const double2 q = *reinterpret_cast<const double2 *>(rhs.p[t] + (long)i * plane + 2 * g);
-                    acc.x += rhs.a[t] * q.x;
-                    acc.y += rhs.a[t] * q.y;
-                }
-            return acc;
-        }
-#endif
         double2 v = load_sys<NF>(rhs, plane, my_perm[i], P, c, s);
         if (conjq) v.y = -v.y;
         const unsigned char code = s_code[i];
@@ -1747,12 +1722,6 @@ solve_forward_lean_kernel(PencilDev P, LuDev L, const RhsSrc rhs, double *__rest
         p = *pvp;
 #pragma unroll
         for (int i = 0; i < KLT; ++i) m[i] = *reinterpret_cast<const double *>(awl + (mo + md[i]));
-#ifdef DDH_SWEEP_ABLATE
-        if (rhs.abl & 4) {                                      // one multiplier load per row
-#pragma unroll
-            for (int i = 1; i < KLT; ++i) m[i] = m[0] * 0.5;
-        }
-#endif
         if (full_border) {
 #pragma unroll
             for (int rb = 0; rb < NBT; ++rb) ab[rb] = abp[rb << 6];
@@ -1892,19 +1861,6 @@ solve_forward_deep_kernel(PencilDev P, LuDev L, const RhsSrc rhs, double *__rest
 
     auto load_row = [&](int i) -> double2 {
         if (s_zero[i]) return make_double2(0.0, 0.0);           // wave-uniform
-#ifdef DDH_SWEEP_ABLATE
-        if (rhs.abl & 1) {                                      // right-hand-side terms from lane-contiguous addresses
-            double2 acc = make_double2(0.0, 0.0);
-#pragma unroll
-            for (int t = 0; t < RHS_MAX; ++t)
-                if (t < rhs.n) {
-                    const double2 q = *reinterpret_cast<const double2 *>(rhs.p[t] + (long)i * plane + 2 * g);
-                    acc.x += rhs.a[t] * q.x;
-                    acc.y += rhs.a[t] * q.y;
-                }
-            return acc;
-        }
-#endif
         double2 v = load_sys<NF>(rhs, plane, my_perm[i], P, c, s);
         if (conjq) v.y = -v.y;
         const unsigned char code = s_code[i];
@@ -2076,10 +2032,7 @@ solve_forward_deep_kernel(PencilDev P, LuDev L, const RhsSrc rhs, double *__rest
     }
 }
 
-#ifdef DDH_SWEEP_ABLATE
-__constant__ int c_abl;          // timing ablations of the backward sweep (DDH_ABL): 2 lane-contiguous stores, 8 one factor load per row
-#endif
-template <int NF, int WT, bool REAL, bool PREF, bool PFUSE = false, int DBG = 0, int MINW = 1>
+template <int NF, int WT, bool REAL, bool PREF, bool PFUSE = false, int MINW = 1>
 __global__ void __launch_bounds__(256, MINW)
 solve_backward_kernel(PencilDev P, LuDev L, double *__restrict__ xout, const double *__restrict__ pband,
                       const unsigned char *__restrict__ skip) {
@@ -2109,9 +2062,6 @@ solve_backward_kernel(PencilDev P, LuDev L, double *__restrict__ xout, const dou
     const long g = (long)blockIdx.x * blockDim.x + threadIdx.x - (long)blk * L.Gp;
     const int row0 = (REAL && L.nsplit > 1) ? blk * L.nh : 0, row1 = (REAL && L.nsplit > 1) ? row0 + L.nh : n;
     const SysId id = sys_id<REAL>(P, L, g);
-    if constexpr ((DBG & 64) != 0) {                 // only the waves solve_backward_ring_kernel leaves out (ring_wave)
-        if (ring_wave(id, (int)(threadIdx.x & 63))) return;
-    }
     if (!id.ok) return;
     const int s = id.s;
     const CellCtx c = cell_ctx(P, id.cell);
@@ -2153,8 +2103,7 @@ solve_backward_kernel(PencilDev P, LuDev L, double *__restrict__ xout, const dou
     const unsigned y_lane = wave_lane_off(y0);
     const unsigned ur_row8 = (unsigned)L.BW << 9, y_row16 = (unsigned)(G * (long)sizeof(double2));
     auto fetch = [&](int j, E *u, double2 &y, double *pr) {
-        if (DBG & 8) y = make_double2(1.0, 2.0);
-        else if constexpr (REAL) y = bload16(y_rs, y_lane, (unsigned)j * y_row16);
+        if constexpr (REAL) y = bload16(y_rs, y_lane, (unsigned)j * y_row16);
         else y = y0[(long)j * G];
         if (PFUSE) {
             const double *prow = pband + (long)j * PBW;
@@ -2162,20 +2111,7 @@ solve_backward_kernel(PencilDev P, LuDev L, double *__restrict__ xout, const dou
             for (int d = 0; d < PBW; ++d) pr[d] = prow[d];
         }
         const E *Ur = ur0 + (long)j * ur_stride;
-        if constexpr (REAL && (DBG & 128) != 0) {
-            // TIMING ONLY (DDH_BWD_DBG=128, results are not a solve): the factor rows addressed as if the storage were
-            // [row][block of 64][entry][lane] instead of [block][row][entry][lane] -- at any time the whole chip then reads
-            // one contiguous 6 MB region per row instead of 9 KB pieces of a thousand streams 15 MB apart
-            const E *rm = (const E *)L.Aw + ((((long)j * L.nblk + (gl >> 6)) * L.BW) << 6) + lu_eoff(L, kl + L.kpad) + ((gl & 63) << 1);
-            const __amdgpu_buffer_rsrc_t rs_j = wave_rsrc(rm);
-            const unsigned ln_j = wave_lane_off(rm);
-#pragma unroll
-            for (int q = 0; 2 * q <= WT; ++q) {
-                const double2 uu = bload16(rs_j, ln_j, (unsigned)(q << 10));
-                u[2 * q] = uu.x;
-                if (2 * q + 1 <= WT) u[2 * q + 1] = uu.y;
-            }
-        } else if constexpr (REAL) {
+        if constexpr (REAL) {
             // pair-packed rows (LuDev::pk; the diagonal sits at an even entry): 16-byte loads, two entries each
             const unsigned urow = (unsigned)j * ur_row8;                                 // uniform
             // pairs beyond the measured fill of this row are exact zeros in every factorization: not loaded (wave-uniform;
@@ -2184,14 +2120,8 @@ solve_backward_kernel(PencilDev P, LuDev L, double *__restrict__ xout, const dou
             const int nq = __builtin_amdgcn_readfirstlane((int)s_nq[j]);
 #pragma unroll
             for (int q = 0; 2 * q <= WT; ++q) {
-#ifdef DDH_SWEEP_ABLATE
-                const bool one = (c_abl & 8) && q > 0;
-#else
-                constexpr bool one = false;
-#endif
                 double2 uu = make_double2(0.0, 0.0);
-                if (((DBG & 1) && q > 0) || one) uu = make_double2(u[0] * 0.5, u[0] * 0.25);
-                else if (q < NQMIN || q < nq) uu = bload16(ur_rs, ur_lane, urow + (unsigned)(q << 10));
+                if (q < NQMIN || q < nq) uu = bload16(ur_rs, ur_lane, urow + (unsigned)(q << 10));
                 u[2 * q] = uu.x;
                 if (2 * q + 1 <= WT) u[2 * q + 1] = uu.y;
             }
@@ -2212,11 +2142,6 @@ solve_backward_kernel(PencilDev P, LuDev L, double *__restrict__ xout, const dou
             if ((code & 2) && s == 1) v = make_double2(-v.x, -v.y);
         }
         if (conjq) v.y = -v.y;
-        if ((DBG & 4) && v.x != 1.2345e300) return;
-        if (DBG & 32) { *reinterpret_cast<double2 *>(xout + (long)j * plane + 2 * g) = v; return; }
-#ifdef DDH_SWEEP_ABLATE
-        if (c_abl & 2) { *reinterpret_cast<double2 *>(xout + (long)j * plane + 2 * g) = v; return; }
-#endif
         store_sys<NF>(xout, plane, my_perm[j], P, c, s, v);
     };
     // rows are processed in pairs; the register window is shifted once per pair (by two).  With PFUSE the emitted value
@@ -2224,16 +2149,9 @@ solve_backward_kernel(PencilDev P, LuDev L, double *__restrict__ xout, const dou
     // band coefficients are the same for every system -> scalar loads.
     auto row_even = [&](int j, const E *u, double2 y, const double *pr) -> double2 {
         double2 acc = y;
-        if constexpr ((DBG & 2) != 0) {
-            int o = 0;
-#pragma unroll
-            for (int d = 0; d < WT; ++d) o |= __double2loint(u[d + 1]);
-            acc.x += (double)o * win[0].x;
-        } else {
 #pragma unroll
         for (int d = 0; d < WT; ++d)
             if (FULL || d < W) El<REAL>::fms2(acc, u[d + 1], win[d]);
-        }
         const double2 xj = El<REAL>::mul2(acc, u[0]);   // reciprocal pivot stored on the diagonal
         double2 v = xj;
         if (PFUSE) {
@@ -2247,16 +2165,9 @@ solve_backward_kernel(PencilDev P, LuDev L, double *__restrict__ xout, const dou
     auto row_odd = [&](int j, const E *u, double2 y, double2 xprev, const double *pr) {
         double2 acc = y;
         El<REAL>::fms2(acc, u[1], xprev);
-        if constexpr ((DBG & 2) != 0) {
-            int o = 0;
-#pragma unroll
-            for (int d = 1; d < WT; ++d) o |= __double2loint(u[d + 1]);
-            acc.x += (double)o * win[0].x;
-        } else {
 #pragma unroll
         for (int d = 1; d < WT; ++d)
             if (FULL || d < W) El<REAL>::fms2(acc, u[d + 1], win[d - 1]);
-        }
         const double2 xj = El<REAL>::mul2(acc, u[0]);
         double2 v = xj;
         if (PFUSE) {
@@ -2267,11 +2178,9 @@ solve_backward_kernel(PencilDev P, LuDev L, double *__restrict__ xout, const dou
                 if (d - 1 < WT) { v.x += pr[d] * win[d - 1].x; v.y += pr[d] * win[d - 1].y; }
         }
         emit(j, v);
-        if constexpr ((DBG & 16) == 0) {
 #pragma unroll
         for (int d = WT - 1; d > 1; --d) win[d] = win[d - 2];
         win[1] = xprev;
-        }
         win[0] = xj;
     };
     int j = row1 - 1;
@@ -2313,9 +2222,6 @@ solve_backward_kernel(PencilDev P, LuDev L, double *__restrict__ xout, const dou
 // the same order: bit-identical to solve_backward_kernel.  Replaces the back substitution of the reference's per-pencil
 // SuperLU solve (libraries/matsolvers.py:126-149).
 // ------------------------------------------------------------------------------------------------
-#ifndef DDH_BWD_DEEP_PD
-#define DDH_BWD_DEEP_PD 2       // register sets of the deep backward sweep: 2 x 40 + the 68 of the window fit 256 registers, 4 do not
-#endif
 template <int WT, int PD>
 __global__ void __launch_bounds__(256, 1)
 solve_backward_deep_kernel(PencilDev P, LuDev L, double *__restrict__ xout, const double *__restrict__ pband,
@@ -2444,222 +2350,6 @@ solve_backward_deep_kernel(PencilDev P, LuDev L, double *__restrict__ xout, cons
             row_even(j - d, u[d], yv[d], pr[d]);
         }
     }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Backward sweep of the real-graded two-axis path with the factor rows and the forward sweep's vector y staged through a
-// per-wave LDS RING filled by LDS-DMA (buffer_load_dwordx4 ... lds), D rows ahead.
-//
-// solve_backward_kernel<2, 17, true, false, true, 0, 4> (the kernel this one replaces at 512^2 pencils) has no prefetch at
-// all: its 128 registers hold the solution window, and a row is "request 9 + 1 loads, wait one HBM round trip, 40 FMAs,
-// store" with only the four waves of a SIMD to hide each other's round trips -- 3.6 TB/s, 0.42 of the wave cycles waiting
-// on memory.  A register prefetch costs the fourth wave (tried: slower).  LDS-DMA loads have NO destination registers, so
-// the rows of the next D steps can be in flight whatever the register file holds:
-//   * the four lanes that share a factorization (P, Q systems of a cell and of its transposed partner: sys_id) used to
-//     request the same 16 bytes four times; here the wave fetches each row ONCE: lane l of DMA instruction i brings entry
-//     pair q = 4 i + l / 16 of the factorization of lane group l % 16 -- 9 x 256 B per row in three instructions -- and every
-//     lane reads its pairs back with broadcast ds_read_b128 (four lanes per address: conflict free);
-//   * y (64 x 16 contiguous bytes per row) comes by one more DMA instruction;
-//   * the loads are hand-issued and waited for with s_waitcnt vmcnt(NV (D - 1)): loads retire in order among themselves,
-//     so "at most the NV (D - 1) operations of the D - 1 younger rows outstanding" means row j has landed whatever the
-//     stores of x in between do (csrc/ddh_gridwave2.hip uses the same argument); past the end of the sweep the wave keeps
-//     requesting its last row so that the count stays uniform.
-// Same arithmetic in the same order as solve_backward_kernel: results are bit-identical (tests/test_gpu_pencil.py).
-// Waves whose lane quads do not share factorizations (the unpaired cells of the axes and the diagonal, a ragged last
-// wave) take the direct-load loop of the old kernel.
-// Replaces the back substitution of the reference's per-pencil SuperLU solve (libraries/matsolvers.py:126-149,
-// core/timesteppers.py:630-643).
-// ------------------------------------------------------------------------------------------------
-typedef __attribute__((address_space(3))) void *ddh_ldsptr;
-
-__device__ __forceinline__ void ring_dma16(unsigned voff, __amdgpu_buffer_rsrc_t rs, unsigned lds_dst, unsigned soff) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(voff), "s"(rs), "s"(lds_dst), "s"(soff)
-                 : "memory");
-}
-template <int N>
-__device__ __forceinline__ void ring_wait() {
-    static_assert(N >= 0 && N <= 32, "vmcnt immediate");
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if constexpr (N == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    else if constexpr (N == 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-    else if constexpr (N == 20) asm volatile("s_waitcnt vmcnt(20)" ::: "memory");
-    else static_assert(N % 4 == 0 && N <= 20, "instantiated depths");
-}
-
-template <int WT>
-struct BwdRing {
-    static constexpr int NQ = (WT + 2) / 2;           // entry pairs of a row from the diagonal on (WT + 1 entries)
-    static constexpr int NI = (NQ + 3) / 4;           // DMA instructions per factor row (four pairs x 16 factorizations each)
-    static constexpr int FB = NQ * 256;               // factor bytes per row and wave
-    static constexpr int SLOT = FB + 1024;            // + y
-    static constexpr int NV = NI + 1;                 // vector-memory operations per row
-};
-
-template <int WT, int D, int MINW>
-__global__ void __launch_bounds__(256, MINW)
-solve_backward_ring_kernel(PencilDev P, LuDev L, double *__restrict__ xout, const double *__restrict__ pband,
-                           const unsigned char *__restrict__ skip) {
-    constexpr int NF = 2;
-    using RG = BwdRing<WT>;
-    static_assert(RG::NV == 4, "ring_wait immediates are multiples of four");
-    static_assert((WT & 1) == 1, "an even number of entries per row: WT + 1");
-    extern __shared__ int s_lds[];
-    const int n = L.n, nb = L.nb, kl = L.kl;
-    int *s_perm = s_lds;
-    int *s_perm2 = s_lds + (L.pair ? n : 0);
-    unsigned char *s_code = (unsigned char *)(s_perm2 + n);
-    unsigned char *s_skip = s_code + n;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        s_perm[i] = L.colperm[i];
-        if (L.pair) s_perm2[i] = L.colperm2[i];
-        s_code[i] = L.col_code[i];
-        s_skip[i] = skip ? (skip[L.colperm[i]] && (!L.pair || skip[L.colperm2[i]])) : 0;
-    }
-    __syncthreads();
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    // this wave's ring: behind the tables, 1 KiB aligned relative to the start of the dynamic LDS
-    const unsigned tab_bytes = (unsigned)(((size_t)n * (L.pair ? 10 : 6) + 1023) & ~(size_t)1023);
-    char *ring = reinterpret_cast<char *>(s_lds) + tab_bytes + (size_t)wave * (D * RG::SLOT);
-    const unsigned ring_lds = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)(ddh_ldsptr)ring);
-
-    const int blk = (L.nsplit > 1) ? __builtin_amdgcn_readfirstlane((int)(((long)blockIdx.x * blockDim.x) / L.Gp)) : 0;
-    const long g = (long)blockIdx.x * blockDim.x + threadIdx.x - (long)blk * L.Gp;
-    const int row0 = (L.nsplit > 1) ? blk * L.nh : 0, row1 = (L.nsplit > 1) ? row0 + L.nh : n;
-    const SysId id = sys_id<true>(P, L, g);
-    if (!ring_wave(id, lane)) return;                // (solve_backward_kernel<..., 64> sweeps this wave's systems)
-    const int s = id.s;
-    const CellCtx c = cell_ctx(P, id.cell);
-    const long G = id.G;
-    const int *my_perm = id.partner ? s_perm2 : s_perm;
-    const bool conjq = id.partner && s == 1;
-    const long plane = P.nx * P.ny;
-
-    double2 win[WT];   // win[d] = x[j+1+d] (graded)
-#pragma unroll
-    for (int d = 0; d < WT; ++d) {
-        win[d] = make_double2(0.0, 0.0);
-        if (d < nb && row1 == n) win[d] = L.scratch[(long)(n + d) * G + g];
-    }
-    unsigned dma_voff, y_lane, ur_row8, y_row16;
-    __amdgpu_buffer_rsrc_t ur_rs, y_rs;
-    {
-        const double *const ur0 = (const double *)L.Aw + lu_aw(L, id.gl, 0, kl);     // row 0, diagonal
-        const double2 *const y0 = L.scratch + g;
-        ur_rs = wave_rsrc(ur0);
-        y_rs = wave_rsrc(y0);
-        y_lane = wave_lane_off(y0);
-        ur_row8 = (unsigned)L.BW << 9;
-        y_row16 = (unsigned)(G * (long)sizeof(double2));
-        // DMA role of this lane: entry pair (lane >> 4) (+ 4 per instruction) of the factorization of lane quad (lane & 15)
-        dma_voff = (unsigned)__shfl((int)wave_lane_off(ur0), 4 * (lane & 15)) + ((unsigned)(lane >> 4) << 10);
-    }
-    // the ring is read through LDS addresses of this lane: pair q of its factorization at q * 256 + (lane / 4) * 16, y behind
-    const unsigned rd_u = (unsigned)(lane >> 2) * 16u, rd_y = (unsigned)RG::FB + (unsigned)lane * 16u;
-
-    auto emit = [&](int j, double2 v) {
-        if (s_skip[j]) return;                           // wave-uniform
-        const unsigned char code = s_code[j];
-        if (code & 1) v = make_double2(-v.y, v.x);
-        if ((code & 2) && s == 1) v = make_double2(-v.x, -v.y);
-        if (conjq) v.y = -v.y;
-        store_sys<NF>(xout, plane, my_perm[j], P, c, s, v);
-    };
-    unsigned slot_issue = 0;                         // byte offset of the slot the next request fills (uniform)
-    auto issue = [&](int j) {
-        const int jj = j < row0 ? row0 : j;          // past the end: the last row again (keeps the operation count uniform)
-        const unsigned dst = ring_lds + slot_issue;
-        const unsigned urow = (unsigned)jj * ur_row8;
-#pragma unroll
-        for (int i = 0; i < RG::NI; ++i) {
-            if (4 * (i + 1) <= RG::NQ) {
-                ring_dma16(dma_voff, ur_rs, dst + 1024u * i, urow + 4096u * i);
-            } else if (4 * i + (lane >> 4) < RG::NQ) {           // the last instruction brings NQ - 4 i pairs
-                ring_dma16(dma_voff, ur_rs, dst + 1024u * i, urow + 4096u * i);
-            }
-        }
-        ring_dma16(y_lane, y_rs, dst + RG::FB, (unsigned)jj * y_row16);
-        slot_issue += RG::SLOT;
-        if (slot_issue == (unsigned)(D * RG::SLOT)) slot_issue = 0;
-    };
-    unsigned slot_read = 0;
-    // One row: x_j = (y_j - sum_d U[j, j + d] x_(j + d)) / U[j, j], emitted as x_j + sum_d P[j, j + d] x_(j + d).
-    // ODD: the row above (j + 1) was solved in this pair and sits in `xprev`, the window still starts at j + 2.
-    // The entry pairs are read from the ring three at a time, between the multiply-adds that consume them (the window
-    // fills the register file: 36 more registers for a whole row would spill).
-    auto row = [&](int j, auto odd_tag, double2 xprev) -> double2 {
-        constexpr bool ODD = decltype(odd_tag)::value;
-        ring_wait<RG::NV * (D - 1)>();               // row j has landed (the D - 1 younger requests may be in flight)
-        const char *rs = ring + slot_read;
-        double2 acc = *reinterpret_cast<const double2 *>(rs + rd_y);
-        double pr[PBW];
-        {
-            const double *prow = pband + (long)j * PBW;
-#pragma unroll
-            for (int d = 0; d < PBW; ++d) pr[d] = prow[d];
-        }
-        double piv = 0.0;
-#pragma unroll
-        for (int q = 0; q < RG::NQ; ++q) {
-            const double2 uu = *reinterpret_cast<const double2 *>(rs + rd_u + 256 * q);
-            // entries 2 q, 2 q + 1 of the row: entry e multiplies x_(j + e)
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int e = 2 * q + h;
-                const double ue = h ? uu.y : uu.x;
-                if (e == 0) {
-                    piv = ue;                            // reciprocal pivot
-                } else if (e <= WT) {
-                    if (ODD) {
-                        if (e == 1) El<true>::fms2(acc, ue, xprev);
-                        else El<true>::fms2(acc, ue, win[e - 2]);
-                    } else {
-                        El<true>::fms2(acc, ue, win[e - 1]);
-                    }
-                }
-            }
-            if (q % 3 == 2) __builtin_amdgcn_sched_barrier(0);
-        }
-        const double2 xj = El<true>::mul2(acc, piv);
-        // the slot has been read by every lane: request row j - D into it
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        issue(j - D);
-        slot_read += RG::SLOT;
-        if (slot_read == (unsigned)(D * RG::SLOT)) slot_read = 0;
-        double2 v = xj;
-        if (ODD) {
-            v.x += pr[0] * xprev.x;
-            v.y += pr[0] * xprev.y;
-#pragma unroll
-            for (int d = 1; d < PBW; ++d)
-                if (d - 1 < WT) { v.x += pr[d] * win[d - 1].x; v.y += pr[d] * win[d - 1].y; }
-        } else {
-#pragma unroll
-            for (int d = 0; d < PBW; ++d)
-                if (d < WT) { v.x += pr[d] * win[d].x; v.y += pr[d] * win[d].y; }
-        }
-        emit(j, v);
-        return xj;
-    };
-    int j = row1 - 1;
-#pragma unroll
-    for (int d = 0; d < D; ++d) issue(j - d);
-    while (j >= row0 + 1) {
-        const double2 xe = row(j, std::false_type(), make_double2(0.0, 0.0));
-        const double2 xo = row(j - 1, std::true_type(), xe);
-#pragma unroll
-        for (int d = WT - 1; d > 1; --d) win[d] = win[d - 2];
-        win[1] = xe;
-        win[0] = xo;
-        j -= 2;
-    }
-    if (j == row0) row(row0, std::false_type(), make_double2(0.0, 0.0));
-    ring_wait<0>();                                  // nothing of this wave may land in LDS after it has gone
 }
 
 // Border unknowns of a forward sweep that ran one thread per (system, block) (LuDev::nsplit > 1): the blocks' partial
@@ -3147,37 +2837,12 @@ static int forward_window(int kl) { return kl <= 6 ? 6 : (kl <= 12 ? 12 : 16); }
 // register window (entries above the diagonal) of the one-thread-per-system backward kernel for an upper bandwidth W
 static int backward_window(int W) { return W <= 17 ? 17 : (W <= 32 ? 32 : (W <= 34 ? 34 : (W <= 48 ? 48 : 64))); }
 
-template <int NF>
-static void choose_variant(const PencilPack *pp, const LuDev &d, int &use_fwd, int &cb) {
-    const PencilDev &P = pp->dev;
-    const int W = d.W;
-    const int coop_mode = pp->coop_mode;
-    const bool coop_auto = coop_mode == 1 && NF > 0;
-    use_fwd = (coop_mode == 2 || (coop_auto && P.G <= 16384)) ? 1 : 0;
-    cb = 0;
-    if (coop_mode == 2 || (coop_auto && P.G <= 1024)) cb = 16;
-    else if (coop_auto && P.G <= 16384) cb = 4;        // (round 3, register-lean sweeps: at 32 768 systems one thread per
-                                                       //  system is faster again, 5.17 vs 5.58 ms -- profiles/r3_strong_scaling_shares.txt)
-    // independent diagonal blocks swept by separate threads (LuDev::nsplit): one thread per (system, block) in both sweeps
-    // beats the cooperative variants from a few thousand systems on (round 4, profiles/r4_strong_scaling_shares.txt, solve
-    // ms per launch at the per-rank shares of 512 x 512 x 256: 16 384 systems: per-thread both 1.97 | per-thread + cb 4:
-    // 2.15 | fwd coop + cb 4: 4.36;  32 768: 2.24 | 3.12 | 8.72;  65 536: 3.28 | 5.03 | 17.3)
-    if (coop_auto && d.nsplit > 1 && P.G > 4096) use_fwd = cb = 0;
-    if (pp->coop_fwd >= 0) use_fwd = pp->coop_fwd;
-    if (pp->coop_cb >= 0) cb = pp->coop_cb;
-    if (NF == 0 || d.kl >= CH || d.nb > 8) use_fwd = 0;
-    if (NF == 0 || (cb != 4 && cb != 16)) cb = 0;
-    if (cb && (W + cb - 1) / cb > (cb == 4 ? 12 : 3)) cb = 0;
-    if (d.n <= 0) use_fwd = cb = 0;
-}
-
 // The lean forward sweep (real-graded factors, two Fourier axes) is instantiated and tested for the windows of the
 // Rayleigh-Benard pencils: kl <= 12, a border of <= 2; other shapes take the general kernel (the wider instantiations fit
 // two waves per SIMD only partly and have no test yet).
 static bool lean_forward_ok(const LuDev &d) {
-    static const int no_lean = getenv("DDH_FWD_LEAN") ? !atoi(getenv("DDH_FWD_LEAN")) : 0;
-    return d.real && d.n > 0 && !no_lean && d.kpad + d.kl == forward_window(d.kl) &&
-           d.rows_aw >= d.n + forward_window(d.kl) && d.kl <= 12 && d.nb <= 2;
+    return d.real && d.n > 0 && d.kpad + d.kl == forward_window(d.kl) && d.rows_aw >= d.n + forward_window(d.kl) &&
+           d.kl <= 12 && d.nb <= 2;
 }
 
 // Few systems: the one-thread-per-(system, block) sweeps would run at less than two wavefronts per SIMD (MI355X: 1024
@@ -3191,201 +2856,239 @@ static bool sweep_deep(const LuDev &d) {
 
 // workgroup size of the deep sweeps: the largest of 256 / 128 / 64 threads that still gives every CU a workgroup (measured at the
 // P = 8 share, 32 768 threads: 2.02 / 1.76 / 1.83 ms per step with 256 / 128 / 64; at 65 536 threads 256 wins: 3.04 / 3.38 / 3.47).
-// DDH_DEEP_BLOCK forces one.
 static unsigned deep_block(long threads) {
-    static const int v = getenv("DDH_DEEP_BLOCK") ? atoi(getenv("DDH_DEEP_BLOCK")) : 0;
-    if (v == 64 || v == 128 || v == 256) return (unsigned)v;
     if (threads / 256 >= 256) return 256u;
     return threads / 128 >= 256 ? 128u : 64u;
 }
 
-// want_p: the caller asks for x = P y (recombination fused into the backward sweep); *did_p tells whether this launch
-// could do it (one-thread-per-system backward kernel of the real-graded 2-axis path with a band table on file).
-template <int NF>
-static int launch_solve(PencilPack *pp, LuFactor *lu, const RhsSrc &rhs, double *x, hipStream_t s, bool want_p = false,
-                        bool *did_p = nullptr) {
+// The kernels of one solve, decided once by sweep_plan: launch_solve executes the plan, solve_recombined_impl learns from
+// it whether the recombination is fused, ddh_pencil_lu_info reports it.
+enum class FwdSweep {
+    coop,         // solve_forward_coop_kernel: CH lanes per system
+    deep,         // solve_forward_deep_kernel: few systems, rows of loads in flight
+    lean_occ4,    // solve_forward_lean_kernel sized for 4 waves per SIMD
+    lean,         // solve_forward_lean_kernel
+    general       // solve_forward_kernel
+};
+enum class BwdSweep {
+    none,         // no band rows
+    coop,         // solve_backward_coop_kernel: cb lanes per system
+    deep,         // solve_backward_deep_kernel (fused recombination): few systems, rows of loads in flight
+    fused_occ4,   // solve_backward_kernel with the fused recombination, sized for 4 waves per SIMD
+    fused,        // solve_backward_kernel with the fused recombination
+    plain         // solve_backward_kernel
+};
+struct SweepPlan {
+    FwdSweep fwd;
+    int fwd_kl, fwd_nb;           // window template arguments: KLT (lean, general), NBT (lean, general, coop)
+    bool border_finish;           // border_finish_kernel after a forward sweep run per (system, block)
+    BwdSweep bwd;
+    int bwd_w;                    // register window WT of the per-thread backward kernels (backward_window)
+    int cb, tt;                   // cooperative backward sweep: lanes per system (CB) and entries per lane (TT)
+    bool fuse_p;                  // x = P y fused into the backward sweep
+    dim3 fwd_grid, fwd_block, bwd_grid, bwd_block;
+    size_t lds_f, lds_b;
+    // the lean forward sweep or its variants: all of them read tile-major terms and report as "lean"
+    bool lean_forward() const { return fwd == FwdSweep::deep || fwd == FwdSweep::lean_occ4 || fwd == FwdSweep::lean; }
+};
+
+// nterms: right-hand-side terms of the solve; want_p: the caller asks for x = P y (the recombination fused into the
+// one-thread-per-system backward kernel of the real-graded 2-axis path, given a band table on file: LuDev::pband)
+static SweepPlan sweep_plan(const PencilPack *pp, const LuDev &d, int nterms, bool want_p) {
     const PencilDev &P = pp->dev;
-    const LuDev &d = lu->dev;
-    if (did_p) *did_p = false;
-    const unsigned blocks = (unsigned)((P.G + 255) / 256);
-    const int W = d.W;
+    const int NF = P.nf, W = d.W;
+    SweepPlan pl{};
     const size_t per_entry = d.pair ? 9 : 5;    // one (two when paired) int permutations + a code byte per row
-    const size_t lds_f = (size_t)(d.N + d.nb) * (per_entry + 1) + 16,     // (+ the zero-row flags of the lean sweep)
- lds_b = (size_t)(d.n > 0 ? d.n : 1) * (per_entry + 2) + 16;   // (+ the skip flags and the row-fill table of the backward sweep)
-    if (lds_f > 64 * 1024) return fail("pencil_solve: system too large for the LDS permutation cache");
-    int use_fwd, cb;
-    choose_variant<NF>(pp, d, use_fwd, cb);
-    if (d.pair) use_fwd = cb = 0;               // partner pencils: one-thread-per-system sweeps only
-    if (use_fwd) {
-        const unsigned cblocks = (d.real && d.nsplit > 1) ? (unsigned)(((long)d.nsplit * d.Gp) / (256 / CH))
-                                                          : (unsigned)((P.G + (256 / CH) - 1) / (256 / CH));
-        // the cooperative sweep's deep branch-free prefetch takes ONE right-hand-side vector: a combination is
-        // materialised first (few systems: the extra pass is small next to the latency-bound sweeps)
-        const double *rhs1 = rhs.p[0];
-        if (rhs.n != 1 || rhs.a[0] != 1.0) {
-            const long nel = (long)P.nrows * P.nx * P.ny;
-            if (!lu->d_rhs_tmp) DDH_HIP(hipMalloc(&lu->d_rhs_tmp, (size_t)nel * sizeof(double) + 16));
-            if (int st0 = ddh_lincomb((double *)lu->d_rhs_tmp, rhs.n, rhs.p, rhs.a, nel, (void *)s)) return st0;
-            rhs1 = (const double *)lu->d_rhs_tmp;
-        }
-#define DDH_CFWD(NBTV)                                                                                             \
-    {                                                                                                              \
-        if (d.real)                                                                                                \
-            hipLaunchKernelGGL((solve_forward_coop_kernel<NF, true, NBTV>), dim3(cblocks), dim3(256), lds_f, s, P, d, rhs1, x); \
-        else                                                                                                       \
-            hipLaunchKernelGGL((solve_forward_coop_kernel<NF, false, NBTV>), dim3(cblocks), dim3(256), lds_f, s, P, d, rhs1, x); \
-    }
-        if constexpr (NF > 0) {
-            if (d.nb <= 2) DDH_CFWD(2) else DDH_CFWD(8)
-            if (d.real && d.nsplit > 1 && d.nb > 0)
-                hipLaunchKernelGGL(border_finish_kernel<NF>, dim3(blocks), dim3(256), 0, s, P, d, x);
-        }
-#undef DDH_CFWD
-    }
-#define DDH_FWD(KLTV, NBTV)                                                                                        \
-    {                                                                                                              \
-        if (d.real)                                                                                                \
-            hipLaunchKernelGGL((solve_forward_kernel<NF, true, KLTV, NBTV>), dim3(blocks), dim3(256), lds_f, s, P, d, rhs, x); \
-        else                                                                                                       \
-            hipLaunchKernelGGL((solve_forward_kernel<NF, false, KLTV, NBTV>), dim3(blocks), dim3(256), lds_f, s, P, d, rhs, x); \
-    }
-    // (few window sizes: every instantiation is a fully unrolled kernel and this file dominates the build time)
-#ifdef DDH_SWEEP_ABLATE
-    // timing ablations (build with -DDDH_SWEEP_ABLATE, select with DDH_ABL = bit mask; results are NOT a solve):
-    //   1 forward: right-hand-side terms from lane-contiguous addresses   2 backward: lane-contiguous stores
-    //   4 forward: one multiplier load per row                            8 backward: one factor load per row
-    // Round 4, 512 x 512 x 256, solve ms per launch (gpurun_out/r4i): 0: 6.77 | 1: 5.36 | 2: 6.04 | 4: 6.77 | 8: 5.62 | all: 3.30
-    static const int abl = getenv("DDH_ABL") ? atoi(getenv("DDH_ABL")) : 0;
-    const_cast<RhsSrc &>(rhs).abl = abl;
-    static bool abl_set = false;
-    if (!abl_set) { (void)hipMemcpyToSymbol(HIP_SYMBOL(c_abl), &abl, sizeof(int)); abl_set = true; }
-#endif
-    bool lean_fwd = false;
+    pl.lds_f = (size_t)(d.N + d.nb) * (per_entry + 1) + 16;          // (+ the zero-row flags of the lean sweep)
+    pl.lds_b = (size_t)(d.n > 0 ? d.n : 1) * (per_entry + 2) + 16;   // (+ the skip flags and the row-fill table of the backward sweep)
+    const unsigned blocks = (unsigned)((P.G + 255) / 256);
     // one thread per (system, block) where the sweep kernels support it (LuDev::nsplit)
-    const unsigned blocks_split = (unsigned)(((long)d.nsplit * d.Gp + 255) / 256);
-    if constexpr (NF == 2) {
-        lean_fwd = !use_fwd && lean_forward_ok(d);
-        if (lean_fwd) {
-#define DDH_LFWD(KLTV, NBTV) \
-    { hipLaunchKernelGGL((solve_forward_lean_kernel<KLTV, NBTV>), dim3(blocks_split), dim3(256), lds_f, s, P, d, rhs, x); }
-            // (block-parallel sweeps double the thread count: 4 waves per SIMD keep every thread resident, DDH_SWEEP_OCC=4)
-            static const int occ4 = getenv("DDH_SWEEP_OCC") ? atoi(getenv("DDH_SWEEP_OCC")) == 4 : 1;
-            if (forward_window(d.kl) == 6 && d.nb == 1 && rhs.n >= 1 && rhs.n <= 4 && sweep_deep(d))     // few systems: PD rows of loads in flight
-                hipLaunchKernelGGL((solve_forward_deep_kernel<6, 1, 4, 4>), dim3(blocks_split * (256 / deep_block((long)d.nsplit * d.Gp))), dim3(deep_block((long)d.nsplit * d.Gp)), lds_f, s, P, d, rhs, x);
-            else if (forward_window(d.kl) == 6 && d.nsplit > 1 && occ4 && d.nb <= 1)
-                hipLaunchKernelGGL((solve_forward_lean_kernel<6, 1, 4>), dim3(blocks_split), dim3(256), lds_f, s, P, d, rhs, x);
-            else if (forward_window(d.kl) == 6 && d.nb <= 1) DDH_LFWD(6, 1)
-            else if (forward_window(d.kl) == 6) DDH_LFWD(6, 2) else DDH_LFWD(12, 2)
-#undef DDH_LFWD
-            if (d.nsplit > 1 && d.nb > 0)
-                hipLaunchKernelGGL(border_finish_kernel<NF>, dim3(blocks), dim3(256), 0, s, P, d, x);
-        }
+    const long threads = (long)d.nsplit * d.Gp;
+    const unsigned blocks_split = (unsigned)((threads + 255) / 256);
+    auto coop_grid = [&](int lanes) {           // workgroups of the cooperative sweeps, `lanes` threads per system
+        return (d.real && d.nsplit > 1) ? (unsigned)(threads / (256 / lanes)) : (unsigned)((P.G + (256 / lanes) - 1) / (256 / lanes));
+    };
+
+    const int coop_mode = pp->coop_mode;
+    const bool coop_auto = coop_mode == 1 && NF > 0;
+    bool coop_fwd = coop_mode == 2 || (coop_auto && P.G <= 16384);
+    int cb = 0;
+    if (coop_mode == 2 || (coop_auto && P.G <= 1024)) cb = 16;
+    else if (coop_auto && P.G <= 16384) cb = 4;        // (round 3, register-lean sweeps: at 32 768 systems one thread per
+                                                       //  system is faster again, 5.17 vs 5.58 ms -- profiles/r3_strong_scaling_shares.txt)
+    // independent diagonal blocks swept by separate threads (LuDev::nsplit): one thread per (system, block) in both sweeps
+    // beats the cooperative variants from a few thousand systems on (round 4, profiles/r4_strong_scaling_shares.txt, solve
+    // ms per launch at the per-rank shares of 512 x 512 x 256: 16 384 systems: per-thread both 1.97 | per-thread + cb 4:
+    // 2.15 | fwd coop + cb 4: 4.36;  32 768: 2.24 | 3.12 | 8.72;  65 536: 3.28 | 5.03 | 17.3)
+    if (coop_auto && d.nsplit > 1 && P.G > 4096) {
+        coop_fwd = false;
+        cb = 0;
     }
-    if (use_fwd || lean_fwd) {
-    } else if (d.nb <= 2) {
-        if (d.kl <= 12) DDH_FWD(12, 2) else DDH_FWD(16, 2)
+    if (pp->coop_fwd >= 0) coop_fwd = pp->coop_fwd != 0;
+    if (pp->coop_cb >= 0) cb = pp->coop_cb;
+    if (NF == 0 || d.kl >= CH || d.nb > 8) coop_fwd = false;
+    if (NF == 0 || (cb != 4 && cb != 16)) cb = 0;
+    if (cb && (W + cb - 1) / cb > (cb == 4 ? 12 : 3)) cb = 0;
+    if (d.n <= 0 || d.pair) {                   // (partner pencils: one-thread-per-system sweeps only)
+        coop_fwd = false;
+        cb = 0;
+    }
+
+    pl.fwd_grid = dim3(blocks);
+    pl.fwd_block = dim3(256);
+    if (coop_fwd) {
+        pl.fwd = FwdSweep::coop;
+        pl.fwd_nb = d.nb <= 2 ? 2 : 8;
+        pl.fwd_grid = dim3(coop_grid(CH));
+        pl.border_finish = d.real && d.nsplit > 1 && d.nb > 0;
+    } else if (NF == 2 && lean_forward_ok(d)) {
+        const bool w6 = forward_window(d.kl) == 6;
+        pl.fwd_kl = w6 ? 6 : 12;
+        pl.fwd_nb = w6 && d.nb <= 1 ? 1 : 2;
+        pl.fwd_grid = dim3(blocks_split);
+        if (w6 && d.nb == 1 && nterms >= 1 && nterms <= 4 && sweep_deep(d)) {     // few systems: PD rows of loads in flight
+            pl.fwd = FwdSweep::deep;
+            pl.fwd_block = dim3(deep_block(threads));
+            pl.fwd_grid = dim3(blocks_split * (256 / pl.fwd_block.x));
+        } else if (w6 && d.nsplit > 1 && d.nb <= 1) {
+            pl.fwd = FwdSweep::lean_occ4;       // (block-parallel sweeps double the thread count: 4 waves per SIMD keep every thread resident)
+        } else {
+            pl.fwd = FwdSweep::lean;
+        }
+        pl.border_finish = d.nsplit > 1 && d.nb > 0;
     } else {
-        if (d.kl <= 12) DDH_FWD(12, 8) else DDH_FWD(16, 8)
+        pl.fwd = FwdSweep::general;
+        pl.fwd_kl = d.kl <= 12 ? 12 : 16;
+        pl.fwd_nb = d.nb <= 2 ? 2 : 8;
     }
-#undef DDH_FWD
+
+    pl.bwd_grid = dim3(blocks_split);
+    pl.bwd_block = dim3(256);
     if (cb) {
-#define DDH_CBWD(TTV, CBV)                                                                                         \
-    {                                                                                                              \
-        const unsigned cblocks = (d.real && d.nsplit > 1) ? (unsigned)(((long)d.nsplit * d.Gp) / (256 / CBV))      \
-                                                          : (unsigned)((P.G + (256 / CBV) - 1) / (256 / CBV));     \
-        if (d.real)                                                                                                \
-            hipLaunchKernelGGL((solve_backward_coop_kernel<NF, TTV, true, CBV>), dim3(cblocks), dim3(256), lds_b, s, P, d, x); \
-        else                                                                                                       \
-            hipLaunchKernelGGL((solve_backward_coop_kernel<NF, TTV, false, CBV>), dim3(cblocks), dim3(256), lds_b, s, P, d, x); \
-    }
+        pl.bwd = BwdSweep::coop;
+        pl.cb = cb;
         const int tt = (W + cb - 1) / cb;
-        if constexpr (NF > 0) {
-            if (cb == 16) {
-                if (tt <= 2) DDH_CBWD(2, 16) else DDH_CBWD(3, 16)
-            } else {
-                if (tt <= 9) DDH_CBWD(9, 4) else DDH_CBWD(12, 4)
-            }
+        pl.tt = cb == 16 ? (tt <= 2 ? 2 : 3) : (tt <= 9 ? 9 : 12);
+        pl.bwd_grid = dim3(coop_grid(cb));
+    } else if (d.n <= 0) {
+        pl.bwd = BwdSweep::none;
+    } else if (NF == 2 && want_p && d.real && d.pband != nullptr && W <= 48) {
+        pl.fuse_p = true;
+        pl.bwd_w = backward_window(W);
+        if (W <= 17 && sweep_deep(d)) {
+            // few systems (less than two waves per SIMD): 2 register sets of rows in flight (2 x 40 + the 68 of the window
+            // fit 256 registers, 4 do not)
+            pl.bwd = BwdSweep::deep;
+            pl.bwd_block = dim3(deep_block(threads));
+            pl.bwd_grid = dim3(blocks_split * (256 / pl.bwd_block.x));
+        } else if (W <= 17 && d.nsplit > 1) {
+            pl.bwd = BwdSweep::fused_occ4;
+        } else {
+            pl.bwd = BwdSweep::fused;
         }
-#undef DDH_CBWD
+    } else {
+        pl.bwd = BwdSweep::plain;
+        pl.bwd_w = backward_window(W);
+        if (!d.real) pl.bwd_grid = dim3(blocks);
     }
-#define DDH_SOLVE(WTV)                                                                                             \
-    {                                                                                                              \
-        if (d.real)                                                                                                \
-            hipLaunchKernelGGL((solve_backward_kernel<NF, WTV, true, false>), dim3(blocks_split), dim3(256), lds_b, s, P, d, x, d.pband, rhs.skip); \
-        else                                                                                                       \
-            hipLaunchKernelGGL((solve_backward_kernel<NF, WTV, false, false>), dim3(blocks), dim3(256), lds_b, s, P, d, x, d.pband, rhs.skip); \
-    }
-    // (window sizes: few instantiations -- every one is a fully unrolled kernel and this file dominates the build time)
-    bool fuse_p = false;
-    if constexpr (NF == 2) fuse_p = want_p && d.real && d.pband != nullptr && d.n > 0 && !cb && W <= 48;
-#define DDH_SOLVE_P(WTV)                                                                                           \
-    { hipLaunchKernelGGL((solve_backward_kernel<NF, WTV, true, false, true>), dim3(blocks_split), dim3(256), lds_b, s, P, d, x, d.pband, rhs.skip); }
-    if (fuse_p) {
-        if constexpr (NF == 2) {
-            static const int occ4 = getenv("DDH_SWEEP_OCC") ? atoi(getenv("DDH_SWEEP_OCC")) == 4 : 1;
-            // DDH_BWD_RING = D: factor rows and y through a per-wave LDS-DMA ring D rows deep (solve_backward_ring_kernel);
-            // 0 = direct loads.  LDS per workgroup: the permutation tables + 4 waves x D x 3.25 KiB.
-            static const int ring = getenv("DDH_BWD_RING") ? atoi(getenv("DDH_BWD_RING")) : 0;
-            const size_t tab = (((size_t)d.n * (d.pair ? 10 : 6)) + 1023) & ~(size_t)1023;
-            if (W <= 17 && d.nsplit > 1 && occ4 && d.pair && ring >= 2 && ring <= 4 && P.G % 4 == 0) {
-                const size_t lds_r = tab + (size_t)4 * ring * BwdRing<17>::SLOT;
-#define DDH_RING(DV, MW)                                                                                                   \
-    {                                                                                                                      \
-        auto kern = solve_backward_ring_kernel<17, DV, MW>;                                                                \
-        if (lds_r > 64 * 1024)                                                                                             \
-            DDH_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r));      \
-        hipLaunchKernelGGL(kern, dim3(blocks_split), dim3(256), lds_r, s, P, d, x, d.pband, rhs.skip);                     \
-    }
-                if (ring == 2) DDH_RING(2, 4)
-                else if (ring == 3) DDH_RING(3, 3)
-                else DDH_RING(4, 2)
-#undef DDH_RING
-                // the waves whose lane quads do not share a factorization (unpaired cells, a ragged last wave)
-                hipLaunchKernelGGL((solve_backward_kernel<NF, 17, true, false, true, 64, 4>), dim3(blocks_split), dim3(256), lds_b, s, P, d, x, d.pband, rhs.skip);
-            } else if (W <= 17 && sweep_deep(d)) {
-                // few systems (less than two waves per SIMD): PD rows of loads in flight in registers
-                static const int pd = getenv("DDH_BWD_DEEP_PD") ? atoi(getenv("DDH_BWD_DEEP_PD")) : DDH_BWD_DEEP_PD;
-                if (pd == 4)
-                    hipLaunchKernelGGL((solve_backward_deep_kernel<17, 4>), dim3(blocks_split * (256 / deep_block((long)d.nsplit * d.Gp))), dim3(deep_block((long)d.nsplit * d.Gp)), lds_b, s, P, d, x, d.pband, rhs.skip);
-                else
-                    hipLaunchKernelGGL((solve_backward_deep_kernel<17, 2>), dim3(blocks_split * (256 / deep_block((long)d.nsplit * d.Gp))), dim3(deep_block((long)d.nsplit * d.Gp)), lds_b, s, P, d, x, d.pband, rhs.skip);
-            } else if (W <= 17 && d.nsplit > 1 && occ4 && getenv("DDH_BWD_DBG") && atoi(getenv("DDH_BWD_DBG")) == 128)
-                hipLaunchKernelGGL((solve_backward_kernel<NF, 17, true, false, true, 128, 4>), dim3(blocks_split), dim3(256), lds_b, s, P, d, x, d.pband, rhs.skip);
-            else if (W <= 17 && d.nsplit > 1 && occ4)
-                hipLaunchKernelGGL((solve_backward_kernel<NF, 17, true, false, true, 0, 4>), dim3(blocks_split), dim3(256), lds_b, s, P, d, x, d.pband, rhs.skip);
-            else if (W <= 17) DDH_SOLVE_P(17)
-            else if (W <= 32) DDH_SOLVE_P(32)
-#ifdef DDH_BWD_ABLATE
-            // timing ablations of the backward sweep (build with -DDDH_BWD_ABLATE; DDH_BWD_DBG = mask: 1 one factor load
-            // per row, 2 no FMAs, 4 no stores, 8 no scratch load, 16 no window shift, 32 stores to lane-contiguous
-            // addresses).  Results are NOT a solve.  Round 3: stores 2.2 ms, factor loads 2.9 ms of
-            // the 4.9 ms sweep, FMAs and window shifts 0.
-            else if (W <= 34 && getenv("DDH_BWD_DBG") && atoi(getenv("DDH_BWD_DBG")) > 0) {
-#define DDH_SOLVE_DBG(V) case V: hipLaunchKernelGGL((solve_backward_kernel<NF, 34, true, false, true, V>), dim3(blocks_split), dim3(256), lds_b, s, P, d, x, d.pband, rhs.skip); break;
-                switch (atoi(getenv("DDH_BWD_DBG"))) {
-                    DDH_SOLVE_DBG(1) DDH_SOLVE_DBG(2) DDH_SOLVE_DBG(4) DDH_SOLVE_DBG(8) DDH_SOLVE_DBG(16) DDH_SOLVE_DBG(32) DDH_SOLVE_DBG(31)
-                    default: DDH_SOLVE_P(34)
-                }
-#undef DDH_SOLVE_DBG
-            }
-#endif
-            else if (W <= 34) DDH_SOLVE_P(34)
-            else DDH_SOLVE_P(48)
-        }
-    } else if (d.n > 0 && !cb) {
-        if (W <= 17) DDH_SOLVE(17)
-        else if (W <= 32) DDH_SOLVE(32)
-        else if (W <= 34) DDH_SOLVE(34)
-        else if (W <= 48) DDH_SOLVE(48)
-        else DDH_SOLVE(64)
-    }
-#undef DDH_SOLVE_P
-#undef DDH_SOLVE
-    DDH_HIP(hipGetLastError());
-    if (did_p) *did_p = fuse_p;
-    return finish_solve<NF>(pp, lu, rhs, x, s, fuse_p ? 1 : 0);
+    return pl;
 }
 
+// (few window sizes: every instantiation is a fully unrolled kernel and this file dominates the build time)
+template <int NF>
+static int launch_solve(PencilPack *pp, LuFactor *lu, const RhsSrc &rhs, double *x, hipStream_t s, const SweepPlan &pl) {
+    const PencilDev &P = pp->dev;
+    const LuDev &d = lu->dev;
+    if (pl.lds_f > 64 * 1024) return fail("pencil_solve: system too large for the LDS permutation cache");
+    const int kl = pl.fwd_kl, nb = pl.fwd_nb, w = pl.bwd_w;
+    switch (pl.fwd) {
+        case FwdSweep::coop:
+            if constexpr (NF > 0) {
+                // the cooperative sweep's deep branch-free prefetch takes ONE right-hand-side vector: a combination is
+                // materialised first (few systems: the extra pass is small next to the latency-bound sweeps)
+                const double *rhs1 = rhs.p[0];
+                if (rhs.n != 1 || rhs.a[0] != 1.0) {
+                    const long nel = (long)P.nrows * P.nx * P.ny;
+                    if (!lu->d_rhs_tmp) DDH_HIP(hipMalloc(&lu->d_rhs_tmp, (size_t)nel * sizeof(double) + 16));
+                    if (int st0 = ddh_lincomb((double *)lu->d_rhs_tmp, rhs.n, rhs.p, rhs.a, nel, (void *)s)) return st0;
+                    rhs1 = (const double *)lu->d_rhs_tmp;
+                }
+                auto k = nb == 2 ? solve_forward_coop_kernel<NF, true, 2> : solve_forward_coop_kernel<NF, true, 8>;
+                if (!d.real) k = nb == 2 ? solve_forward_coop_kernel<NF, false, 2> : solve_forward_coop_kernel<NF, false, 8>;
+                hipLaunchKernelGGL(k, pl.fwd_grid, pl.fwd_block, pl.lds_f, s, P, d, rhs1, x);
+            }
+            break;
+        case FwdSweep::deep:
+            if constexpr (NF == 2)
+                hipLaunchKernelGGL((solve_forward_deep_kernel<6, 1, 4, 4>), pl.fwd_grid, pl.fwd_block, pl.lds_f, s, P, d, rhs, x);
+            break;
+        case FwdSweep::lean_occ4:
+            if constexpr (NF == 2)
+                hipLaunchKernelGGL((solve_forward_lean_kernel<6, 1, 4>), pl.fwd_grid, pl.fwd_block, pl.lds_f, s, P, d, rhs, x);
+            break;
+        case FwdSweep::lean:
+            if constexpr (NF == 2) {
+                auto k = kl == 12 ? solve_forward_lean_kernel<12, 2>
+                                  : (nb == 1 ? solve_forward_lean_kernel<6, 1> : solve_forward_lean_kernel<6, 2>);
+                hipLaunchKernelGGL(k, pl.fwd_grid, pl.fwd_block, pl.lds_f, s, P, d, rhs, x);
+            }
+            break;
+        case FwdSweep::general: {
+            auto k = kl == 12 ? (nb == 2 ? solve_forward_kernel<NF, true, 12, 2> : solve_forward_kernel<NF, true, 12, 8>)
+                              : (nb == 2 ? solve_forward_kernel<NF, true, 16, 2> : solve_forward_kernel<NF, true, 16, 8>);
+            if (!d.real)
+                k = kl == 12 ? (nb == 2 ? solve_forward_kernel<NF, false, 12, 2> : solve_forward_kernel<NF, false, 12, 8>)
+                             : (nb == 2 ? solve_forward_kernel<NF, false, 16, 2> : solve_forward_kernel<NF, false, 16, 8>);
+            hipLaunchKernelGGL(k, pl.fwd_grid, pl.fwd_block, pl.lds_f, s, P, d, rhs, x);
+            break;
+        }
+    }
+    if constexpr (NF > 0)
+        if (pl.border_finish)
+            hipLaunchKernelGGL(border_finish_kernel<NF>, dim3((unsigned)((P.G + 255) / 256)), dim3(256), 0, s, P, d, x);
+    switch (pl.bwd) {
+        case BwdSweep::none:
+            break;
+        case BwdSweep::coop:
+            if constexpr (NF > 0) {
+                auto k = pl.cb == 16 ? (pl.tt == 2 ? solve_backward_coop_kernel<NF, 2, true, 16> : solve_backward_coop_kernel<NF, 3, true, 16>)
+                                     : (pl.tt == 9 ? solve_backward_coop_kernel<NF, 9, true, 4> : solve_backward_coop_kernel<NF, 12, true, 4>);
+                if (!d.real)
+                    k = pl.cb == 16 ? (pl.tt == 2 ? solve_backward_coop_kernel<NF, 2, false, 16> : solve_backward_coop_kernel<NF, 3, false, 16>)
+                                    : (pl.tt == 9 ? solve_backward_coop_kernel<NF, 9, false, 4> : solve_backward_coop_kernel<NF, 12, false, 4>);
+                hipLaunchKernelGGL(k, pl.bwd_grid, pl.bwd_block, pl.lds_b, s, P, d, x);
+            }
+            break;
+        case BwdSweep::deep:
+            if constexpr (NF == 2)
+                hipLaunchKernelGGL((solve_backward_deep_kernel<17, 2>), pl.bwd_grid, pl.bwd_block, pl.lds_b, s, P, d, x, d.pband, rhs.skip);
+            break;
+        case BwdSweep::fused_occ4:
+            if constexpr (NF == 2)
+                hipLaunchKernelGGL((solve_backward_kernel<NF, 17, true, false, true, 4>), pl.bwd_grid, pl.bwd_block, pl.lds_b, s, P, d, x, d.pband, rhs.skip);
+            break;
+        case BwdSweep::fused:
+            if constexpr (NF == 2) {
+                auto k = w == 17 ? solve_backward_kernel<NF, 17, true, false, true> : w == 32 ? solve_backward_kernel<NF, 32, true, false, true>
+                       : w == 34 ? solve_backward_kernel<NF, 34, true, false, true> : solve_backward_kernel<NF, 48, true, false, true>;
+                hipLaunchKernelGGL(k, pl.bwd_grid, pl.bwd_block, pl.lds_b, s, P, d, x, d.pband, rhs.skip);
+            }
+            break;
+        case BwdSweep::plain: {
+            auto k = w == 17 ? solve_backward_kernel<NF, 17, true, false> : w == 32 ? solve_backward_kernel<NF, 32, true, false>
+                   : w == 34 ? solve_backward_kernel<NF, 34, true, false> : w == 48 ? solve_backward_kernel<NF, 48, true, false>
+                   : solve_backward_kernel<NF, 64, true, false>;
+            if (!d.real)
+                k = w == 17 ? solve_backward_kernel<NF, 17, false, false> : w == 32 ? solve_backward_kernel<NF, 32, false, false>
+                  : w == 34 ? solve_backward_kernel<NF, 34, false, false> : w == 48 ? solve_backward_kernel<NF, 48, false, false>
+                  : solve_backward_kernel<NF, 64, false, false>;
+            hipLaunchKernelGGL(k, pl.bwd_grid, pl.bwd_block, pl.lds_b, s, P, d, x, d.pband, rhs.skip);
+            break;
+        }
+    }
+    DDH_HIP(hipGetLastError());
+    return finish_solve<NF>(pp, lu, rhs, x, s, pl.fuse_p ? 1 : 0);
+}
 
 // Per-row upper width of the factors: wrow[j] = max over all factorizations of the last non-zero offset d of
 // U(j, j + d).  Partial pivoting can fill up to kl extra super-diagonals, but rows where no factorization
@@ -3394,10 +3097,10 @@ constexpr int LUW_ROWS = 32;      // rows per workgroup of lu_width_kernel
 
 template <bool REAL>
 __global__ void __launch_bounds__(256)
-lu_width_kernel(LuDev L, int *__restrict__ wrow, long only_blk = -1) {     // only_blk >= 0: that block of 64 factorizations alone (diagnostic)
+lu_width_kernel(LuDev L, int *__restrict__ wrow) {
     typedef typename El<REAL>::T E;
     const long gl = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool act = gl < L.GL && (only_blk < 0 || (gl >> 6) == only_blk);
+    const bool act = gl < L.GL;
     const E *Aw = (const E *)L.Aw;
     // blockIdx.y: a chunk of LUW_ROWS rows (a thread's scan of a row is a chain of dependent loads: the chunks run side by side)
     const int j0 = (int)blockIdx.y * LUW_ROWS, j1 = min(L.n, j0 + LUW_ROWS);
@@ -3453,9 +3156,6 @@ int ddh_pencil_create(ddh_handle *pack, const ddh_pencil_geom *geom) {
     d.ky = (const double *)pp->d_ky;
     if (d.nf >= 1) pp->kx_h.assign(geom->kx_h, geom->kx_h + d.ncx);
     if (d.nf == 2) pp->ky_h.assign(geom->ky_h, geom->ky_h + d.ncy);
-    if (const char *e = getenv("DDH_SOLVE_COOP")) pp->coop_mode = atoi(e);
-    if (const char *e = getenv("DDH_COOP_FWD")) pp->coop_fwd = atoi(e);
-    if (const char *e = getenv("DDH_COOP_CB")) pp->coop_cb = atoi(e);
     *pack = register_handle(pp);
     return 0;
 }
@@ -3948,14 +3648,13 @@ static int factor_impl(ddh_handle pack, int matM_id, int matL_id, double a, doub
         st = upload_vec(&lu->d_flag_cells, lu->flag_cells.data(), lu->flag_cells.size());
         if (st) return st;
     }
-    // the fill of U, row by row, for the backward sweep (LuDev::wrow); DDH_BWD_ROW_FILL=0: every pair is loaded
-    static const bool row_fill = !(getenv("DDH_BWD_ROW_FILL") && atoi(getenv("DDH_BWD_ROW_FILL")) == 0);
+    // the fill of U, row by row, for the backward sweep (LuDev::wrow)
     lu->dev.wrow = nullptr;
-    if (row_fill && real && n > 0) {
+    if (real && n > 0) {
         if (!lu->d_wrow) DDH_HIP(hipMalloc(&lu->d_wrow, (size_t)n * sizeof(int)));
         DDH_HIP(hipMemsetAsync(lu->d_wrow, 0, (size_t)n * sizeof(int), s));
         hipLaunchKernelGGL(lu_width_kernel<true>, dim3((unsigned)((lu->dev.GL + 255) / 256), (unsigned)((n + LUW_ROWS - 1) / LUW_ROWS)),
-                           dim3(256), 0, s, lu->dev, (int *)lu->d_wrow, -1L);
+                           dim3(256), 0, s, lu->dev, (int *)lu->d_wrow);
         DDH_HIP(hipGetLastError());
         lu->dev.wrow = (const int *)lu->d_wrow;
     }
@@ -4088,9 +3787,10 @@ int ddh_pencil_solve_lincomb(ddh_handle pack, int lu_id, int nterms, const doubl
     }
     LuFactor *lu = pp->lus[lu_id];
     hipStream_t s = as_stream(stream);
-    if (pp->dev.nf == 2) return launch_solve<2>(pp, lu, r, x, s);
-    if (pp->dev.nf == 1) return launch_solve<1>(pp, lu, r, x, s);
-    return launch_solve<0>(pp, lu, r, x, s);
+    const SweepPlan pl = sweep_plan(pp, lu->dev, nterms, false);
+    if (pp->dev.nf == 2) return launch_solve<2>(pp, lu, r, x, s, pl);
+    if (pp->dev.nf == 1) return launch_solve<1>(pp, lu, r, x, s, pl);
+    return launch_solve<0>(pp, lu, r, x, s, pl);
 }
 
 // band table of the recombination matrix P (a registered constant real matrix) in the logical ordering of an LU;
@@ -4153,14 +3853,9 @@ int ddh_pencil_solve_recombined_tiled(ddh_handle pack, int lu_id, int nterms, co
     if (lu_id < 0 || lu_id >= (int)pp->lus.size()) return fail("pencil_solve: bad LU id");
     if (pp->dev.nf != 2 || (pp->dev.nx & 7) || (pp->dev.ny & 7))
         return fail("pencil_solve_recombined_tiled: two Fourier axes with storage sizes that are multiples of 8");
-    {
-        int uf, cbv;
-        choose_variant<2>(pp, pp->lus[lu_id]->dev, uf, cbv);
-        if (pp->lus[lu_id]->dev.pair) uf = 0;
-        if (uf || !lean_forward_ok(pp->lus[lu_id]->dev))
-            return fail("pencil_solve_recombined_tiled: this factorization does not run the lean forward sweep, the only one "
-                        "that reads tile-major terms (ddh_pencil_lu_info)");
-    }
+    if (!sweep_plan(pp, pp->lus[lu_id]->dev, nterms, false).lean_forward())
+        return fail("pencil_solve_recombined_tiled: this factorization does not run the lean forward sweep, the only one "
+                    "that reads tile-major terms (ddh_pencil_lu_info)");
     return solve_recombined_impl(pack, lu_id, nterms, xs_h, alpha_h, p_mat_id, work, x, zero_rows, skip_rows, 1, stream);
 }
 
@@ -4186,22 +3881,11 @@ static int solve_recombined_impl(ddh_handle pack, int lu_id, int nterms, const d
     r.tiled = terms_tiled;
     LuFactor *lu = pp->lus[lu_id];
     hipStream_t s = as_stream(stream);
-    static const bool no_fuse = getenv("DDH_NO_PFUSE") != nullptr;
-    bool did = false;
     int st;
-    if (pp->dev.nf == 2 && !no_fuse) {
-        if ((st = build_pband(pp, lu, p_mat_id))) return st;
-        // the fused kernel writes x directly; if this launch cannot fuse, the sweeps must write the work vector instead:
-        // decide first (same logic as launch_solve) by a dry query
-        int uf, cbv;
-        choose_variant<2>(pp, lu->dev, uf, cbv);
-        if (lu->dev.pband != nullptr && lu->dev.real && !cbv && lu->dev.W <= 48 && lu->dev.n > 0) {
-            st = launch_solve<2>(pp, lu, r, x, s, true, &did);
-            if (st) return st;
-            if (did) return 0;
-            return fail("pencil_solve_recombined: internal error (fused variant not taken)");
-        }
-    }
+    if (pp->dev.nf == 2 && (st = build_pband(pp, lu, p_mat_id))) return st;
+    // the fused kernel writes x directly; if the plan cannot fuse, the sweeps write the work vector instead
+    const SweepPlan pl = sweep_plan(pp, lu->dev, nterms, true);
+    if (pl.fuse_p) return launch_solve<2>(pp, lu, r, x, s, pl);
     r.skip = nullptr;       // (the unfused path recombines from `work` with a mat-vec: every row of it must be written)
     if (pp->dev.nf == 1 && lu->d_binv && lu->dev.real && lu->dev.n == lu->dev.nsplit * lu->dev.nh) {
         const LuDev &d = lu->dev;
@@ -4210,9 +3894,9 @@ static int solve_recombined_impl(ddh_handle pack, int lu_id, int nterms, const d
                            s, pp->dev, d, r, lu->d_binv, work);
         DDH_HIP(hipGetLastError());
         st = finish_solve<1>(pp, lu, r, work, s, 0);
-    } else if (pp->dev.nf == 2) st = launch_solve<2>(pp, lu, r, work, s);
-    else if (pp->dev.nf == 1) st = launch_solve<1>(pp, lu, r, work, s);
-    else st = launch_solve<0>(pp, lu, r, work, s);
+    } else if (pp->dev.nf == 2) st = launch_solve<2>(pp, lu, r, work, s, pl);
+    else if (pp->dev.nf == 1) st = launch_solve<1>(pp, lu, r, work, s, pl);
+    else st = launch_solve<0>(pp, lu, r, work, s, pl);
     if (st) return st;
     PostSolve none;
     memset(&none, 0, sizeof(none));
@@ -4231,10 +3915,9 @@ int ddh_pencil_lu_row_widths(ddh_handle pack, int lu_id, int *wrow_h) {
     DDH_HIP(hipMalloc((void **)&dw, d.n * sizeof(int)));
     DDH_HIP(hipMemset(dw, 0, d.n * sizeof(int)));
     const unsigned blocks = (unsigned)((d.GL + 255) / 256);
-    const long only = getenv("DDH_LUW_BLOCK") ? atol(getenv("DDH_LUW_BLOCK")) : -1;      // (diagnostic: one block of 64)
     const dim3 wgrid(blocks, (unsigned)((d.n + LUW_ROWS - 1) / LUW_ROWS));
-    if (d.real) hipLaunchKernelGGL(lu_width_kernel<true>, wgrid, dim3(256), 0, 0, d, dw, only);
-    else hipLaunchKernelGGL(lu_width_kernel<false>, wgrid, dim3(256), 0, 0, d, dw, only);
+    if (d.real) hipLaunchKernelGGL(lu_width_kernel<true>, wgrid, dim3(256), 0, 0, d, dw);
+    else hipLaunchKernelGGL(lu_width_kernel<false>, wgrid, dim3(256), 0, 0, d, dw);
     DDH_HIP(hipGetLastError());
     DDH_HIP(hipMemcpy(wrow_h, dw, d.n * sizeof(int), hipMemcpyDeviceToHost));
     (void)hipFree(dw);
@@ -4246,15 +3929,9 @@ int ddh_pencil_lu_info(ddh_handle pack, int lu_id, int *info_h) {
     if (!pp) return -1;
     if (lu_id < 0 || lu_id >= (int)pp->lus.size()) return fail("pencil_lu_info: bad LU id");
     const LuDev &d = pp->lus[lu_id]->dev;
-    int use_fwd = 0, cb = 0;
-    switch (pp->dev.nf) {
-        case 0: choose_variant<0>(pp, d, use_fwd, cb); break;
-        case 1: choose_variant<1>(pp, d, use_fwd, cb); break;
-        default: choose_variant<2>(pp, d, use_fwd, cb); break;
-    }
-    if (d.pair) use_fwd = cb = 0;
-    const bool lean = pp->dev.nf == 2 && !use_fwd && lean_forward_ok(d);
-    const int v[12] = {d.n, d.nb, d.kl, d.ku, d.W, d.BW, d.nsplit, d.nh, use_fwd ? 2 : (lean ? 1 : 0), cb, d.pair, d.real};
+    const SweepPlan pl = sweep_plan(pp, d, 1, false);
+    const int fwd = pl.fwd == FwdSweep::coop ? 2 : (pl.lean_forward() ? 1 : 0);
+    const int v[12] = {d.n, d.nb, d.kl, d.ku, d.W, d.BW, d.nsplit, d.nh, fwd, pl.cb, d.pair, d.real};
     for (int i = 0; i < 12; ++i) info_h[i] = v[i];
     return 0;
 }

@@ -427,8 +427,8 @@ int ddh_pencil_solve_recombined_sparse(ddh_handle pack, int lu_id, int nterms, c
 /* Sweep variant used by ddh_pencil_solve (all variants compute the same factorization's solution; they differ in how
  * many lanes share one system).  mode 1 (default): chosen by the number of systems; 0: one
  * thread per system; 2: cooperative (16 lanes) in both sweeps.  fwd = 0 / 1 and backward_lanes = 0 / 4 / 16 override
- * the forward and backward kernel individually, -1 leaves the choice to `mode`.  The defaults can also be preset with
- * the environment variables DDH_SOLVE_COOP / DDH_COOP_FWD / DDH_COOP_CB, which are read ONCE, by ddh_pencil_create. */
+ * the forward and backward kernel individually, -1 leaves the choice to `mode`.  Partner pencils
+ * (ddh_pencil_set_pairing) always take the one-thread-per-system sweeps. */
 int ddh_pencil_set_solve_variant(ddh_handle pack, int mode, int fwd, int backward_lanes);
 /* Partner pencils.  For a problem that is symmetric under the exchange of its two Fourier axes (same box length and
  * size along x and y, isotropic equations: 3-D Rayleigh-Benard is), the pencil matrices obey

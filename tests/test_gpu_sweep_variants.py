@@ -1,9 +1,7 @@
-"""GPU: every selectable variant of the per-thread sweeps takes bit-identical steps (csrc/ddh_pencil.hip, round 6):
-the plain kernels, the deep-prefetch kernels for few systems (solve_forward_deep_kernel / solve_backward_deep_kernel, two and
-four register sets in the backward sweep) and the backward sweep through the per-wave LDS-DMA ring
-(solve_backward_ring_kernel + solve_backward_kernel<..., 64> for the waves whose lane quads do not share a factorization),
-two, three and four rows deep.  The switches are read once per process, so every variant steps in a subprocess; the plain
-variant is also compared with the reference's end state (tests/golden/config_rb3d_endstate_128x128x64.npz).
+"""GPU: both variants of the per-thread sweeps take bit-identical steps (csrc/ddh_pencil.hip): the plain kernels and the
+deep-prefetch kernels for few systems (solve_forward_deep_kernel / solve_backward_deep_kernel), selected with DDH_SWEEP_DEEP.
+The switch is read once per process, so every variant steps in a subprocess; the plain variant is also compared with the
+reference's end state (tests/golden/config_rb3d_endstate_128x128x64.npz).
 Same arithmetic in the same order in all of them: the reference's per-pencil LU solves (libraries/matsolvers.py:126-149)."""
 import json
 import os
@@ -45,17 +43,14 @@ def _run(env_extra, shape):
     return json.loads(line[7:])
 
 
-VARIANTS = [{"DDH_SWEEP_DEEP": "1"}, {"DDH_SWEEP_DEEP": "1", "DDH_BWD_DEEP_PD": "4"},
-            {"DDH_SWEEP_DEEP": "0", "DDH_BWD_RING": "2"}, {"DDH_SWEEP_DEEP": "0", "DDH_BWD_RING": "3"},
-            {"DDH_SWEEP_DEEP": "0", "DDH_BWD_RING": "4"}]
+VARIANTS = [{"DDH_SWEEP_DEEP": "1"}]
 
 
 @pytest.mark.parametrize("shape", [(128, 128, 64), (64, 96, 32)])
 def test_sweep_variants_take_bit_identical_steps(shape):
-    """128 x 128 x 64: partner pencils (x <-> y symmetric; the ring kernel's case); 64 x 96 x 32: unpaired factorizations (the
-    ring kernel must stand aside, the deep kernels run)."""
+    """128 x 128 x 64: partner pencils (x <-> y symmetric); 64 x 96 x 32: unpaired factorizations."""
     common = {"DDH_PAIR_MIN": "0"}                      # (pairing is reserved for >= 65 536 systems by default)
-    base = _run(dict(common, DDH_SWEEP_DEEP="0", DDH_BWD_RING="0"), shape)
+    base = _run(dict(common, DDH_SWEEP_DEEP="0"), shape)
     assert base["forward"] == "lean" and base["nsplit"] == 2
     assert bool(base["pair"]) == (shape[0] == shape[1])
     for env in VARIANTS:

@@ -51,28 +51,6 @@ for step in "$@"; do
                 python tools/bench_configs.py sphere 2>&1 | grep -v "^\[" | tail -3 | tee -a $OUT/sphere.txt ;;
     configs)    python tools/bench_configs.py --json > $OUT/configs.json 2> $OUT/configs.err; tail -5 $OUT/configs.json ;;
     offsize)    python tools/bench_configs.py --offsize > $OUT/offsize.json 2> $OUT/offsize.err; python tools/show_offsize.py $OUT/offsize.json ;;
-    shares)     # per-rank shares of the strong-scaled problem on one GPU, sweep variants A/B (profiles/*_strong_scaling_shares.txt)
-                for sz in 256,512,256 128,512,256 64,512,256; do
-                  for var in "default:" "per-thread:DDH_SOLVE_COOP=0" "per-thread-unsplit:DDH_SOLVE_COOP=0 DDH_SPLIT_THREADS=0" "coop-fwd+cb4:DDH_COOP_FWD=1 DDH_COOP_CB=4" "cb4:DDH_COOP_FWD=0 DDH_COOP_CB=4"; do
-                    name=${var%%:*}; envs=${var#*:}
-                    env $envs python bench.py --full --size $sz --steps 10 --warmup 3 --repeats 1 --no-cpu-baseline --no-parity --no-cfl > $OUT/share_${sz//,/x}_$name.json 2>/dev/null
-                    python - $OUT/share_${sz//,/x}_$name.json "$sz $name" <<'PY'
-import json, sys
-try:
-    d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
-    k = d["kernels"]
-    print("%-34s ms/step %6.2f  solve %5.2f  fused-y %5.2f  others %5.2f" % (sys.argv[2], d["ms_per_step"], k["pencil_solve"]["avg_ms"],
-          k.get("rfft_bilinear_fused", {}).get("avg_ms", 0.0), d["ms_per_step"] - 2 * k["pencil_solve"]["avg_ms"] - 2 * k.get("rfft_bilinear_fused", {}).get("avg_ms", 0.0)))
-except Exception as e:
-    print(sys.argv[2], "failed:", e)
-PY
-                  done
-                done ;;
-    ring-ab)    # backward sweep: direct loads against the LDS-DMA ring, depth 2 / 3 / 4 (DDH_BWD_RING), same box
-                for r in 0 2 3 4; do
-                  DDH_BWD_RING=$r python bench.py --full --steps 10 --warmup 3 --repeats 1 --no-cpu-baseline --no-cfl > $OUT/bench_ring$r.json 2> $OUT/bench_ring$r.err
-                  echo "DDH_BWD_RING=$r"; bench_line $OUT/bench_ring$r.json
-                done ;;
     emu)        # one rank of the P-rank run on this GPU, loop-back exchange (profiles/r6_rank_emulation.txt)
                 python tools/rank_emulation.py --ranks 2,4,8 --rank 1 --steps 10 --warmup 3 ${ONE_GPU_MS:+--single-gpu-ms $ONE_GPU_MS} > $OUT/rank_emulation.jsonl 2> $OUT/rank_emulation.txt; cat $OUT/rank_emulation.txt ;;
     emu-final)  # final table: windows 1 / 2 with and without the emulated wire, P = 2, 4, 8
@@ -97,26 +75,15 @@ PY
                 python -m pytest tests/test_gpu_multirank.py -x -q -m gpu > $OUT/pytest_multirank.txt 2>&1; tail -3 $OUT/pytest_multirank.txt
                 for P in 8 4; do for v in 1 2 4; do
                   echo "P=$P DDH_A2A_WINDOWS=$v"; env DDH_A2A_WINDOWS=$v python tools/rank_emulation.py --ranks $P --rank 1 --steps 10 --warmup 8 --link-gbps 75 2>&1 >/dev/null | cut -c1-220; done; done 2>&1 | tee $OUT/emu_windows_ab.txt ;;
-    bwd-rowmajor) # timing experiment: the backward sweep reading the factor rows as if stored row-major over the blocks
-                for v in 0 128; do DDH_BWD_DBG=$v python bench.py --full --steps 10 --warmup 3 --repeats 1 --no-cpu-baseline --no-cfl --no-parity > $OUT/bench_bwddbg$v.json 2> $OUT/bench_bwddbg$v.err
-                  echo "DDH_BWD_DBG=$v"; bench_line $OUT/bench_bwddbg$v.json; done ;;
     deep-ab)    # few-system sweeps: deep register prefetch (solve_*_deep_kernel) against the plain kernels, bit identity + time
-                for sz in 64,512,256 128,512,256; do for v in 0 1 "1 DDH_BWD_DEEP_PD=4"; do
+                for sz in 64,512,256 128,512,256; do for v in 0 1; do
                   env DDH_SWEEP_DEEP=$v python bench.py --full --size $sz --steps 10 --warmup 3 --repeats 1 --no-cpu-baseline --no-cfl --no-parity > $OUT/bench_deep.json 2> $OUT/bench_deep.err
                   echo "size $sz DDH_SWEEP_DEEP=$v"; bench_line $OUT/bench_deep.json; done; done
                 DDH_SWEEP_DEEP=1 python -m pytest tests/test_gpu_pencil.py tests/test_gpu_reference_pencils.py -x -q -m gpu > $OUT/pytest_deep.txt 2>&1; tail -3 $OUT/pytest_deep.txt ;;
     deep-big)   # the deep sweeps beyond their default range: 2 and 4 waves per SIMD worth of threads
-                for sz in 256,512,256 512,512,256; do for v in 0 1 "1 DDH_BWD_DEEP_PD=4"; do
+                for sz in 256,512,256 512,512,256; do for v in 0 1; do
                   env DDH_SWEEP_DEEP=$v python bench.py --full --size $sz --steps 10 --warmup 3 --repeats 1 --no-cpu-baseline --no-cfl --no-parity > $OUT/bench_deep.json 2> $OUT/bench_deep.err
                   echo "size $sz DDH_SWEEP_DEEP=$v"; bench_line $OUT/bench_deep.json; done; done ;;
-    rowfill-ab) # backward sweep: entry pairs beyond the measured fill of a U row not loaded (LuDev::wrow), against all pairs
-                for v in 0 1 0 1; do DDH_BWD_ROW_FILL=$v python bench.py --full --steps 10 --warmup 3 --repeats 1 --no-cpu-baseline --no-cfl > $OUT/bench_rowfill$v.json 2> $OUT/bench_rowfill$v.err
-                  echo "DDH_BWD_ROW_FILL=$v"; bench_line $OUT/bench_rowfill$v.json; done ;;
-    emu-block)  # the deep sweeps' workgroup size at the P = 4 / 8 shares
-                for b in 256 128 64; do echo "DDH_DEEP_BLOCK=$b"; DDH_DEEP_BLOCK=$b python tools/rank_emulation.py --ranks 4,8 --rank 1 --steps 10 --warmup 3 2>&1 >/dev/null | cut -c1-150; done ;;
-    emu-ring)   # the P = 4 / 8 shares with the backward sweep's LDS-DMA ring, depth 2 / 3 / 4
-                for r in 2 3 4; do echo "DDH_BWD_RING=$r" | tee -a $OUT/rank_emulation_ring.txt
-                  DDH_BWD_RING=$r python tools/rank_emulation.py --ranks 4,8 --rank 1 --steps 10 --warmup 3 2>&1 >/dev/null | tee -a $OUT/rank_emulation_ring.txt; done ;;
     tests-new)  python -m pytest tests/test_gpu_wave_transforms.py tests/test_gpu_comm.py tests/test_gpu_pencil.py tests/test_gpu_reference_pencils.py tests/test_gpu_baseline_sizes.py -x -q -m gpu -s > $OUT/pytest_new.txt 2>&1; tail -5 $OUT/pytest_new.txt; grep "end state vs" $OUT/pytest_new.txt ;;
     *)          echo "running: $step"; bash -c "$step" ;;
   esac
