@@ -30,15 +30,9 @@ __device__ __forceinline__ int lpad(int i) { return i + (i >> 4); }
 // Twiddles come from a two-level table held in LDS (W^q = hi[q >> 5] * lo[q & 31], < 1 KiB per
 // workgroup): the per-butterfly table reads from global memory competed with the streaming traffic for
 // L1 and cost an L2 round trip per pass.  Powers w^t are built by binary products (depth <= 4).
-__host__ __device__ __forceinline__ int tw_entries(int N, int direct) { return direct ? N : 32 + (N >> 5) + 1; }
 template <typename P>
-__device__ __forceinline__ void load_twiddles(const P &p, double2 *tw_lo, double2 *&tw_hi, int tid, int T) {
-    if (p.twdirect) {
-        for (int i = tid; i < p.N; i += T) tw_lo[i] = p.tw[i];
-        tw_hi = nullptr;
-        return;
-    }
-    for (int i = tid; i < 32 + (p.N >> 5) + 1; i += T) {
+__device__ __forceinline__ void load_twiddles(const P &p, double2 *tw_lo, double2 *tw_hi, int tid, int T) {
+    for (int i = tid; i < tw_entries(p.N); i += T) {
         if (i < 32) {
             tw_lo[i] = p.tw[i < p.N ? i : 0];
         } else {
@@ -48,7 +42,7 @@ __device__ __forceinline__ void load_twiddles(const P &p, double2 *tw_lo, double
     }
 }
 __device__ __forceinline__ double2 lds_twiddle(const double2 *tw_lo, const double2 *tw_hi, int q, int sign) {
-    double2 w = tw_hi ? cmul(tw_hi[q >> 5], tw_lo[q & 31]) : tw_lo[q];
+    double2 w = cmul(tw_hi[q >> 5], tw_lo[q & 31]);
     if (sign > 0) w.y = -w.y;
     return w;
 }
@@ -56,7 +50,7 @@ __device__ __forceinline__ double2 lds_twiddle(const double2 *tw_lo, const doubl
 template <int R>
 __device__ __forceinline__ void fft_pass(double2 *buf, int ld, int B, int N, int Ns, const FastDiv &fd_nb,
                                          const FastDiv &fd_ns, const double2 *tw_lo, const double2 *tw_hi, int sign,
-                                         int tid, int T, int dbg = 0) {
+                                         int tid, int T) {
     constexpr int MAXI = (12 + R - 1) / R;   // ceil(12 / R): at least 12 (at most 16) complex values staged per thread
     const int nb = N / R;
     const int total = nb * B;
@@ -89,7 +83,7 @@ __device__ __forceinline__ void fft_pass(double2 *buf, int ld, int B, int N, int
 #pragma unroll
                 for (int t = 0; t < R; ++t) v[it][t] = x[lpad(j + t * nb)];
             }
-            if (Ns > 1 && !(dbg & 1)) {
+            if (Ns > 1) {
                 double2 wp[R];    // wp[t] = w^t
                 wp[1] = lds_twiddle(tw_lo, tw_hi, k * twstep, sign);
 #pragma unroll
@@ -101,7 +95,7 @@ __device__ __forceinline__ void fft_pass(double2 *buf, int ld, int B, int N, int
 #pragma unroll
                 for (int t = 1; t < R; ++t) v[it][t] = cmul(v[it][t], wp[t]);
             }
-            if (!(dbg & 1)) butterfly<R>(v[it], sign);
+            butterfly<R>(v[it], sign);
             const int j0 = (j - k) * R + k;
             wl[it] = line * ld;
             wj[it] = lin_w ? lpad(j0) : j0;
@@ -128,19 +122,18 @@ __device__ __forceinline__ void fft_pass(double2 *buf, int ld, int B, int N, int
 __device__ __forceinline__ void lds_fft(double2 *buf, const FftDev &p, const double2 *tw_lo, const double2 *tw_hi,
                                         int sign, int tid, int T, int nlines_wg = 0) {
     int Ns = 1;
-    if (p.dbg & 2) return;
     const int B = nlines_wg > 0 ? nlines_wg : p.B;   // lines (pairs) in the workgroup's buffer
     for (int i = 0; i < p.nradix; ++i) {
         const int R = p.radix[i];
         switch (R) {
-            case 2: fft_pass<2>(buf, p.ld, B, p.N, Ns, p.fd_nb[i], p.fd_ns[i], tw_lo, tw_hi, sign, tid, T, p.dbg); break;
-            case 3: fft_pass<3>(buf, p.ld, B, p.N, Ns, p.fd_nb[i], p.fd_ns[i], tw_lo, tw_hi, sign, tid, T, p.dbg); break;
-            case 4: fft_pass<4>(buf, p.ld, B, p.N, Ns, p.fd_nb[i], p.fd_ns[i], tw_lo, tw_hi, sign, tid, T, p.dbg); break;
-            case 5: fft_pass<5>(buf, p.ld, B, p.N, Ns, p.fd_nb[i], p.fd_ns[i], tw_lo, tw_hi, sign, tid, T, p.dbg); break;
-            case 6: fft_pass<6>(buf, p.ld, B, p.N, Ns, p.fd_nb[i], p.fd_ns[i], tw_lo, tw_hi, sign, tid, T, p.dbg); break;
-            case 8: fft_pass<8>(buf, p.ld, B, p.N, Ns, p.fd_nb[i], p.fd_ns[i], tw_lo, tw_hi, sign, tid, T, p.dbg); break;
-            case 16: fft_pass<16>(buf, p.ld, B, p.N, Ns, p.fd_nb[i], p.fd_ns[i], tw_lo, tw_hi, sign, tid, T, p.dbg); break;
-            default: fft_pass<7>(buf, p.ld, B, p.N, Ns, p.fd_nb[i], p.fd_ns[i], tw_lo, tw_hi, sign, tid, T, p.dbg); break;
+            case 2: fft_pass<2>(buf, p.ld, B, p.N, Ns, p.fd_nb[i], p.fd_ns[i], tw_lo, tw_hi, sign, tid, T); break;
+            case 3: fft_pass<3>(buf, p.ld, B, p.N, Ns, p.fd_nb[i], p.fd_ns[i], tw_lo, tw_hi, sign, tid, T); break;
+            case 4: fft_pass<4>(buf, p.ld, B, p.N, Ns, p.fd_nb[i], p.fd_ns[i], tw_lo, tw_hi, sign, tid, T); break;
+            case 5: fft_pass<5>(buf, p.ld, B, p.N, Ns, p.fd_nb[i], p.fd_ns[i], tw_lo, tw_hi, sign, tid, T); break;
+            case 6: fft_pass<6>(buf, p.ld, B, p.N, Ns, p.fd_nb[i], p.fd_ns[i], tw_lo, tw_hi, sign, tid, T); break;
+            case 8: fft_pass<8>(buf, p.ld, B, p.N, Ns, p.fd_nb[i], p.fd_ns[i], tw_lo, tw_hi, sign, tid, T); break;
+            case 16: fft_pass<16>(buf, p.ld, B, p.N, Ns, p.fd_nb[i], p.fd_ns[i], tw_lo, tw_hi, sign, tid, T); break;
+            default: fft_pass<7>(buf, p.ld, B, p.N, Ns, p.fd_nb[i], p.fd_ns[i], tw_lo, tw_hi, sign, tid, T); break;
         }
         Ns *= R;
     }
@@ -207,13 +200,13 @@ constexpr int LDU = 6;   // global loads staged per thread before the dependent 
 
 __device__ __forceinline__ int dct_perm(int j, int N) { return (j & 1) ? (N - 1 - (j >> 1)) : (j >> 1); }
 
-template <int MODE, bool INNER, int TMAX, int MINW>
-__global__ void __launch_bounds__(TMAX, MINW)
+template <int MODE, bool INNER, int TMAX>
+__global__ void __launch_bounds__(TMAX, 1)
 fft_axis_kernel(FftDev p, const double *__restrict__ src, double *__restrict__ dst, long outer, long inner,
                 long npairs, unsigned blocks_per_outer) {
     extern __shared__ double2 lds[];
     double2 *buf = lds;                 // [B][ld]
-    double2 *tw_lo = lds + p.B * p.ld;  // [32]        W^q          (or the full table [N])
+    double2 *tw_lo = lds + p.B * p.ld;  // [32]        W^q
     double2 *tw_hi = tw_lo + 32;        // [N/32 + 1]  W^(32 q)
     load_twiddles(p, tw_lo, tw_hi, threadIdx.x, blockDim.x);
     // Chebyshev normalisation (Appendix A of SURVEY.md; transforms.py:720-724, 737-746, 823-826, 844-860)
@@ -225,18 +218,7 @@ fft_axis_kernel(FftDev p, const double *__restrict__ src, double *__restrict__ d
     auto bscale_of = [&](int k) -> double { return k == 0 ? bs0 : ((k & 1) ? -bs1 : bs1); };
     auto half_of = [&](int k) -> double2 { return p.half[k]; };   // small table, read once per element
     const int tid = threadIdx.x, T = blockDim.x;
-    unsigned bid = xcd_swizzle(blockIdx.x, gridDim.x);
-    if (INNER && p.spread_s > 1) {
-        // Strided lines whose rows are a large power of two apart map a contiguous window of workgroups
-        // to few HBM channels: spread each XCD's run of workgroups over its whole address range, in
-        // chunks of spread_c neighbours (which share DRAM pages).
-        const unsigned per = gridDim.x >> 3, S = (unsigned)p.spread_s, c = (unsigned)p.spread_c;
-        if (per > 0 && bid < (per << 3) && per % (S * c) == 0) {
-            const unsigned x = bid / per, l = bid - x * per;
-            const unsigned chunk = l / c, r = l - chunk * c, nchunk = per / c;
-            bid = x * per + ((chunk % S) * (nchunk / S) + chunk / S) * c + r;
-        }
-    }
+    const unsigned bid = xcd_swizzle(blockIdx.x, gridDim.x);
     PairIO<INNER> io;
     long q0;
     if (INNER) {
@@ -250,8 +232,6 @@ fft_axis_kernel(FftDev p, const double *__restrict__ src, double *__restrict__ d
     }
     const int N = p.N, M = p.M, B = p.B, ld = p.ld;
     const double invN = 1.0 / (double)N;
-    long long t_start = 0, t_loaded = 0, t_fft = 0;
-    if (p.prof) t_start = clock64();
 
     // Dual output (RFFT_BWD only, ddh_rfft_backward_dual): a second pass transforms the SAME coefficient tile again with
     // another derivative scale into dst2 -- the field and its derivative along the axis from one HBM read of the
@@ -267,9 +247,7 @@ fft_axis_kernel(FftDev p, const double *__restrict__ src, double *__restrict__ d
     dst = (pass == 0) ? dst_first : p.dst2;
     if (pass) __syncthreads();          // the LDS tile of the first pass has been stored
     // ---------------------------------------------------------------- load + pre-process
-    if (p.dbg & 4) {
-        // timing ablation: no loads
-    } else if (MODE == RFFT_FWD && !INNER && (N % 2 == 0)) {
+    if (MODE == RFFT_FWD && !INNER && (N % 2 == 0)) {
         const int Nh = N / 2;
         for (int b = 0; b < B; ++b) {
             const bool has_a = (q0 + b < npairs);
@@ -645,17 +623,13 @@ fft_axis_kernel(FftDev p, const double *__restrict__ src, double *__restrict__ d
         }
     }
     __syncthreads();
-    if (p.prof) t_loaded = clock64();
 
     // ---------------------------------------------------------------- FFT in LDS
     const int sign = (MODE == RFFT_FWD || MODE == CHEB_FWD || MODE == CFFT_FWD) ? -1 : +1;
     lds_fft(buf, p, tw_lo, tw_hi, sign, tid, T);
-    if (p.prof) t_fft = clock64();
 
     // ---------------------------------------------------------------- post-process + store
-    if (p.dbg & 16) {
-        // timing ablation: no stores
-    } else if (MODE == RFFT_BWD && !INNER && (N % 2 == 0)) {
+    if (MODE == RFFT_BWD && !INNER && (N % 2 == 0)) {
         // contiguous lines: each thread stores two consecutive grid points of line a and of line b (16 B each)
         const int Nh = N / 2;
         for (int b = 0; b < B; ++b) {
@@ -772,16 +746,6 @@ fft_axis_kernel(FftDev p, const double *__restrict__ src, double *__restrict__ d
         }
     }
     }   // pass
-    if (p.prof) {
-        __syncthreads();
-        if (tid == 0) {
-            const long long t_end = clock64();
-            atomicAdd(&p.prof[0], (unsigned long long)(t_loaded - t_start));
-            atomicAdd(&p.prof[1], (unsigned long long)(t_fft - t_loaded));
-            atomicAdd(&p.prof[2], (unsigned long long)(t_end - t_fft));
-            atomicAdd(&p.prof[3], 1ull);
-        }
-    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -884,7 +848,12 @@ fused_rfft_bilinear_kernel(FftDev p, FusedArgs f, long nlines, long npairs) {
         for (int i = 0; i < FUSED_NC; ++i) s_out[i] = f.out[i];
     }
     __syncthreads();                                      // argument tables and twiddles are visible
-    const long q = (p.rot & 2) ? (long)blockIdx.x : (long)xcd_swizzle(blockIdx.x, gridDim.x);   // line pair of this workgroup
+    const long q = (long)xcd_swizzle(blockIdx.x, gridDim.x);   // line pair of this workgroup
+    // Workgroup-uniform bound on the swizzled index (never taken: the grid is npairs workgroups).  It also decides the
+    // register allocation of this kernel, which sits at the 256-VGPR limit: without a run-time condition on q the
+    // compiler (ROCm 7.2) spills 56 / 116 / 284 B per lane in the <3,1> / <3,3> / <6,1> instances instead of 0 / 0 / 24
+    // (tests/test_kernel_resources.py::test_workgroup_grid_stage_does_not_gain_scratch holds the bounds).
+    if (q >= npairs) return;
     const int N = p.N, ld = p.ld;
     // LDS address of this thread's i-th grid point
     int addr[PTS];
@@ -902,29 +871,15 @@ fused_rfft_bilinear_kernel(FftDev p, FusedArgs f, long nlines, long npairs) {
         for (int ia = 0; ia < FUSED_NA; ++ia) areg[ia][i] = make_double2(0.0, 0.0);
     }
     const int na = f.na, nbatch = f.nbatch;
-    long long pt[4] = {0, 0, 0, 0}, tc = 0;   // debug phase clocks: wait, load, fft, rest
-    if (p.prof) tc = clock64();
-#define DDH_TICK(slot)                      \
-    if (p.prof) {                           \
-        const long long now = clock64();    \
-        pt[slot] += now - tc;               \
-        tc = now;                           \
-    }
 #pragma unroll 1
     for (int ib = 0; ib < nbatch; ++ib) {
         const int l0 = s_bbeg[ib], cnt = s_bbeg[ib + 1] - l0;
-        DDH_TICK(3)
         __syncthreads();                     // buf is free
-        DDH_TICK(0)
-        if (!(p.dbg & 4)) {
 #pragma unroll
-            for (int g = 0; g < G; ++g)
-                if (g < cnt) fused_load_lines(buf + g * ld, p, s_src[l0 + g], s_dscale[l0 + g], q, nlines, tid, T);
-        }
+        for (int g = 0; g < G; ++g)
+            if (g < cnt) fused_load_lines(buf + g * ld, p, s_src[l0 + g], s_dscale[l0 + g], q, nlines, tid, T);
         __syncthreads();
-        DDH_TICK(1)
         lds_fft(buf, p, tw_lo, tw_hi, +1, tid, T, cnt);
-        DDH_TICK(2)
         if (l0 < na) {
             // `a` operands stay in registers (run-time index, static register selection)
 #pragma unroll
@@ -947,7 +902,7 @@ fused_rfft_bilinear_kernel(FftDev p, FusedArgs f, long nlines, long npairs) {
                 double2 wv[PTS];
 #pragma unroll
                 for (int i = 0; i < PTS; ++i) wv[i] = (addr[i] >= 0) ? buf[g * ld + addr[i]] : make_double2(0.0, 0.0);
-                const int t1 = (p.dbg & 8) ? 0 : s_tbeg[l0 + g + 1];
+                const int t1 = s_tbeg[l0 + g + 1];
 #pragma unroll 1
                 for (int t = s_tbeg[l0 + g]; t < t1; ++t) {
                     const double cf = s_coef[t];
@@ -974,26 +929,11 @@ fused_rfft_bilinear_kernel(FftDev p, FusedArgs f, long nlines, long npairs) {
                 acc[i] = make_double2(0.0, 0.0);
             }
             __syncthreads();
-            DDH_TICK(3)
             lds_fft(buf, p, tw_lo, tw_hi, -1, tid, T, 1);
-            DDH_TICK(2)
             fused_store_lines(buf, p, s_out[oc], q, nlines, tid, T);
         }
     }
-    DDH_TICK(3)
-#undef DDH_TICK
-    if (p.prof && tid == 0)
-        for (int i = 0; i < 4; ++i) atomicAdd(&p.prof[i], (unsigned long long)pt[i]);
 }
-
-// ddh_fftwave.hip: wave-per-four-pairs transforms along a strided axis; 0 = launched, 1 = shape not covered, < 0 error
-int wave_axis_try(int mode, const FftDev &d, const double *src, double *dst, long outer, long inner, double *dst2,
-                  const double *dvec, double dscale, double dscale2, hipStream_t st);
-// ddh_gridwave.hip: wave-per-line variant of the fused grid stage for N = 128*C
-// ddh_fftwave.hip: the same lane code along a CONTIGUOUS axis (Chebyshev, N = 192: the shell's radial transforms)
-int wave_contig_try(int mode, const FftDev &d, const double *src, double *dst, long outer, double *dst2, hipStream_t st);
-bool gridwave_supported(const FftDev &d);
-int launch_gridwave(const FftDev &d, const FusedArgs &f, long nlines, hipStream_t st);
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -1045,11 +985,9 @@ static int make_plan(ddh_handle *out, int kind, int n_grid, int n_coeff, int nba
             delete pl;
             return fail("plan_rfft: n_coeff must be even");
         }
-        int KN = (n_grid - 1) / 2, KM = (n_coeff - 1) / 2;
-        d.K = KN < KM ? KN : KM;
+        d.K = fourier_kmax(n_grid, n_coeff);
     } else if (kind == K_CFFT) {
-        int KN = (n_grid - 1) / 2, KM = (n_coeff - 1) / 2;
-        d.K = KN < KM ? KN : KM;
+        d.K = fourier_kmax(n_grid, n_coeff);
     }
     const int N = n_grid, M = n_coeff;
     std::vector<double2> tw(N), half(N);
@@ -1135,42 +1073,6 @@ static int make_plan(ddh_handle *out, int kind, int n_grid, int n_coeff, int nba
         return st;
     }
     d.ld = N + (N >> 4) + 1;
-    d.rot = getenv("DDH_FUSED_ROT") ? atoi(getenv("DDH_FUSED_ROT")) : 0;
-    d.dbg = getenv("DDH_FFT_DBG") ? atoi(getenv("DDH_FFT_DBG")) : 0;
-    d.spread_s = 0;
-    d.spread_c = 1;
-    if (const char *sp = getenv("DDH_FFT_SPREAD")) {
-        d.spread_s = atoi(sp);
-        const char *cm = strchr(sp, ',');
-        d.spread_c = cm ? atoi(cm + 1) : 1;
-        if (d.spread_c < 1) d.spread_c = 1;
-    }
-    d.twdirect = (getenv("DDH_FFT_TWDIRECT") && atoi(getenv("DDH_FFT_TWDIRECT"))) ? 1 : 0;
-    if (const char *rs = getenv("DDH_FFT_RADIX")) {   // tuning aid: "16,16,3" replaces the schedule when it fits N
-        int r[MAX_RADIX_PASSES], n = 0, prod = 1;
-        for (const char *c = rs; *c && n < MAX_RADIX_PASSES;) {
-            r[n] = atoi(c);
-            prod *= r[n] > 0 ? r[n] : 1;
-            ++n;
-            while (*c && *c != ',') ++c;
-            if (*c == ',') ++c;
-        }
-        bool ok = prod == N;
-        for (int i = 0; i < n; ++i)
-            ok = ok && (r[i] == 2 || r[i] == 3 || r[i] == 4 || r[i] == 5 || r[i] == 6 || r[i] == 7 || r[i] == 8 || r[i] == 16);
-        if (ok) {
-            d.nradix = n;
-            for (int i = 0; i < n; ++i) d.radix[i] = r[i];
-        }
-    }
-    d.prof = nullptr;
-    if (getenv("DDH_FFT_PROF") && atoi(getenv("DDH_FFT_PROF"))) {
-        void *pm = nullptr;
-        if (hipMalloc(&pm, 4 * sizeof(unsigned long long)) == hipSuccess) {
-            (void)hipMemset(pm, 0, 4 * sizeof(unsigned long long));
-            d.prof = (unsigned long long *)pm;
-        }
-    }
     d.fdN.set((unsigned)N);
     d.fdM.set((unsigned)M);
     d.fdMh.set((unsigned)(M / 2 > 0 ? M / 2 : 1));
@@ -1189,80 +1091,43 @@ static int make_plan(ddh_handle *out, int kind, int n_grid, int n_coeff, int nba
 
 static long g_wave_launches = 0;      // ddh_fft_wave_launches
 
+// One transform call: transform_plan (ddh_fftwave.hip) decides the kernel and its launch shape, this executes it.
 template <int MODE>
 static int launch(FftPlan *pl, const double *src, double *dst, long outer, long inner, void *stream,
                   double dscale = 0.0, double *dst2 = nullptr, double dscale2 = 0.0, const double *dvec = nullptr) {
     if (outer <= 0 || inner <= 0) return 0;
+    const TransformPlan tp = transform_plan(pl->dev, MODE, outer, inner, dst2 != nullptr, dscale != 0.0, dvec != nullptr,
+                                            src == dst || src == dst2);
+    if (tp.error) return fail(tp.error);
     FftDev d = pl->dev;
     d.dscale = dscale;
     d.dst2 = dst2;
     d.dscale2 = dscale2;
     d.dvec = dvec;
-    const bool is_cfft = (MODE == CFFT_FWD || MODE == CFFT_BWD);
-    const bool inner_mode = inner > 1;
-    if (!is_cfft && inner_mode) {
-        // strided axis at an instantiated size: one wavefront per four line pairs (ddh_fftwave.hip)
-        const int wst = wave_axis_try(MODE, d, src, dst, outer, inner, dst2, dvec, dscale, dscale2, as_stream(stream));
-        if (wst == 0) ++g_wave_launches;
-        if (wst <= 0) return wst;
-    }
-    if (!is_cfft && !inner_mode) {
-        const int wst = wave_contig_try(MODE, d, src, dst, outer, dst2, as_stream(stream));
-        if (wst == 0) ++g_wave_launches;
-        if (wst <= 0) return wst;
-    }
-    if (d.xb && inner_mode) return fail("x-blocked stage layout (ddh_fft_set_stage_layout): only the strided-axis wave kernels at their "
-                          "instantiated sizes read / write it -- this transform would have used another kernel");
-    if (d.ctile_nseg) return fail("tile-major coefficient rows (ddh_cheb_forward_tiled, ddh_fft_set_coeff_tiled): only the strided-axis "
-                                  "Chebyshev wave kernels at their instantiated sizes read / write that layout");
-    long npairs;
-    if (is_cfft)
-        npairs = inner_mode ? inner : outer;
-    else
-        npairs = inner_mode ? (inner + 1) / 2 : (outer + 1) / 2;
-    // lines per workgroup: 64 B of contiguous data per row when strided; bounded by LDS (<= 64 KiB
-    // so that at least two workgroups share a CU) and by 12 staged values per thread.
-    const int N = d.N;
-    const size_t per_line = (size_t)d.ld * sizeof(double2);
-    static const int envB = getenv("DDH_FFT_B") ? atoi(getenv("DDH_FFT_B")) : 0;
-    static const long lds_cap = getenv("DDH_FFT_LDSCAP") ? atol(getenv("DDH_FFT_LDSCAP")) : 64 * 1024;
-    int B = inner_mode ? 8 : 4;      // strided: 128-byte contiguous segments per row when LDS allows
-    if (!inner_mode) {
-        // contiguous SHORT lines (the shell's radial transforms: 192 <- 128): 4 line pairs are a tile of a few KiB, the
-        // workgroup's fixed costs (twiddle tables, barriers) dominate -- up to 16 pairs while a thread keeps <= 12 items
-        while (B < 16 && (long)N * (2 * B) <= 12L * 256) B *= 2;
-    }
-    if (envB > 0) B = envB;
-    while (B > 1 && (long)(per_line * B) > lds_cap) B /= 2;
-    if ((long)B > npairs) B = (int)npairs;
-    if (per_line * B > 160 * 1024) return fail("transform: axis too long for the LDS kernel");
-    int T = 256;
-    while ((long)N * B > 12L * T && T < 1024) T *= 2;
-    if ((long)N * B > 12L * T) return fail("transform: axis too long for the LDS kernel (registers)");
-    d.B = B;
-    d.fdB.set((unsigned)B);
-    const unsigned bpo = (unsigned)((npairs + B - 1) / B);
-    const unsigned long nblocks = inner_mode ? (unsigned long)bpo * (unsigned long)outer : bpo;
-    if (nblocks > 0x7fffffffUL) return fail("transform: grid too large");
-    const size_t lds = per_line * B + (size_t)tw_entries(N, d.twdirect) * sizeof(double2);
     hipStream_t s = as_stream(stream);
-#define DDH_FFT_LAUNCH(INNERV, TMAXV, MINWV)                                                                \
-    {                                                                                                       \
-        auto kern = fft_axis_kernel<MODE, INNERV, TMAXV, MINWV>;                                            \
-        if (lds > 64 * 1024)                                                                                \
-            DDH_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,     \
-                                        (int)lds));                                                         \
-        hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(T), lds, s, d, src, dst, outer, inner,       \
-                           npairs, bpo);                                                                    \
+    if (tp.wave()) ++g_wave_launches;
+    switch (tp.kernel) {
+        case TransformKernel::cheb_wave: return launch_cheb_wave(tp, d, src, dst, inner, s);
+        case TransformKernel::rfft_wave: return launch_rfft_wave(tp, d, src, dst, inner, s);
+        case TransformKernel::cheb_contig_wave: return launch_cheb_contig_wave(tp, d, src, dst, outer, s);
+        case TransformKernel::workgroup: break;
     }
-    // register budget follows the real block size (a 1024-thread bound would cap at 64 VGPRs and spill)
-    static const int occ4 = (getenv("DDH_FFT_OCC4") && atoi(getenv("DDH_FFT_OCC4"))) ? 1 : 0;
-    if (inner_mode) {
-        if (T <= 256) { if (occ4) DDH_FFT_LAUNCH(true, 256, 4) else DDH_FFT_LAUNCH(true, 256, 1) }
-        else DDH_FFT_LAUNCH(true, 1024, 1)
+    d.B = tp.B;
+    d.fdB.set((unsigned)tp.B);
+    // TMAX: the register budget follows the real block size (a 1024-thread bound caps at 64 VGPRs and spills)
+#define DDH_FFT_LAUNCH(INNERV, TMAXV)                                                                       \
+    {                                                                                                       \
+        auto kern = fft_axis_kernel<MODE, INNERV, TMAXV>;                                                   \
+        if (tp.lds > 64 * 1024)                                                                             \
+            DDH_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,     \
+                                        (int)tp.lds));                                                      \
+        hipLaunchKernelGGL(kern, dim3(tp.grid), dim3(tp.block), tp.lds, s, d, src, dst, outer, inner,       \
+                           tp.npairs, tp.bpo);                                                              \
+    }
+    if (tp.inner) {
+        if (tp.block <= 256) DDH_FFT_LAUNCH(true, 256) else DDH_FFT_LAUNCH(true, 1024)
     } else {
-        if (T <= 256) { if (occ4) DDH_FFT_LAUNCH(false, 256, 4) else DDH_FFT_LAUNCH(false, 256, 1) }
-        else DDH_FFT_LAUNCH(false, 1024, 1)
+        if (tp.block <= 256) DDH_FFT_LAUNCH(false, 256) else DDH_FFT_LAUNCH(false, 1024)
     }
 #undef DDH_FFT_LAUNCH
     DDH_HIP(hipGetLastError());
@@ -1376,18 +1241,6 @@ mmt_mfma_kernel(const double *__restrict__ mat, const double *__restrict__ in, d
 using namespace ddh;
 
 extern "C" {
-
-/* debug only (not part of the documented ABI): average cycles per workgroup in the three phases */
-int ddh_debug_fft_prof(ddh_handle plan, double *out4) {
-    FftPlan *pl = (FftPlan *)lookup_handle(plan, H_FFT);
-    if (!pl || !pl->dev.prof) return fail("no profiling buffer (set DDH_FFT_PROF=1 before planning)");
-    unsigned long long h[4];
-    DDH_HIP(hipMemcpy(h, pl->dev.prof, sizeof(h), hipMemcpyDeviceToHost));
-    for (int i = 0; i < 3; ++i) out4[i] = h[3] ? (double)h[i] / (double)h[3] : 0.0;
-    out4[3] = (double)h[3];
-    (void)hipMemset(pl->dev.prof, 0, sizeof(h));
-    return 0;
-}
 
 int ddh_plan_rfft(ddh_handle *plan, int n_grid, int n_coeff) {
     return make_plan(plan, K_RFFT, n_grid, n_coeff, 0, nullptr, nullptr);
@@ -1547,42 +1400,17 @@ int ddh_rfft_bilinear_fused(ddh_handle plan, int na, const double *const *a_h, c
         nterms > FUSED_TERMS)
         return fail("rfft_bilinear_fused: operand counts out of range (na<=3, nb<=12, nc<=4, terms<=32)");
     if (nlines <= 0) return 0;
+    const FusedPlan fp = fused_plan(pl->dev, nlines);       // ddh_gridwave.hip
+    if (fp.error) return fail(fp.error);
     FftDev d = pl->dev;
-    const int T = FUSED_T;
-    // A WIDER INTERNAL GRID where this grid size has no wave kernel (round 6).  The stage maps coefficient lines to
-    // coefficient lines; its grid never reaches memory.  Bilinear products of lines with modes <= K are free of aliasing in
-    // the retained modes on ANY grid of N' > 3 K points, so the stage may run on the smallest N' >= N the wave kernels are
-    // instantiated for (N' = 128 C) and returns the same coefficients up to round-off -- e.g. 192-point lines (128 modes) on
-    // 256 points, 576-point lines (384 modes) on 768 -- instead of the workgroup-per-line-pair kernel below (0.05-0.12 of the
-    // HBM rate, profiles/r6_offsize_configs.txt).  DDH_FUSED_WIDER=0 keeps the plan's own size.
-    static const bool wider = !(getenv("DDH_FUSED_WIDER") && atoi(getenv("DDH_FUSED_WIDER")) == 0);
-    if (wider && !gridwave_supported(d)) {
-        if (!pl->fused_alt) {
-            static const int sizes[] = {256, 384, 512, 768, 1024};
-            for (int Np : sizes) {
-                FftDev t = d;
-                t.N = Np;
-                if (Np >= d.N && Np > 3 * d.K && gridwave_supported(t)) {
-                    ddh_handle h = 0;
-                    if (int st = make_plan(&h, K_RFFT, Np, d.M, 0, nullptr, nullptr)) return st;
-                    pl->fused_alt = h;
-                    break;
-                }
-            }
-        }
-        if (pl->fused_alt) {
-            FftPlan *alt = (FftPlan *)lookup_handle(pl->fused_alt, H_FFT);
-            if (!alt) return -1;
-            d = alt->dev;
-        }
+    if (fp.N != d.N) {          // the stage works on a wider grid: that size's plan, owned by this one
+        if (!pl->fused_alt)
+            if (int st = make_plan(&pl->fused_alt, K_RFFT, fp.N, d.M, 0, nullptr, nullptr)) return st;
+        FftPlan *alt = (FftPlan *)lookup_handle(pl->fused_alt, H_FFT);
+        if (!alt) return -1;
+        d = alt->dev;
     }
-    if ((long)d.N > 6L * T) return fail("rfft_bilinear_fused: axis too long for the fused kernel");
-    // operands transformed together: 3 when the points fit 3 per thread and 12 staged values per thread
-    static const int envG = getenv("DDH_FUSED_G") ? atoi(getenv("DDH_FUSED_G")) : 0;
-    int G = ((long)d.N <= 3L * T && 3L * d.N <= 12L * T) ? 3 : 1;
-    if (envG == 1) G = 1;
-    const bool wave_path = gridwave_supported(d);     // one wavefront per line (ddh_gridwave.hip)
-    if (wave_path) G = 1;
+    const int G = fp.G;
     d.B = 1;
     d.fdB.set(1u);
     int order[FUSED_TERMS];
@@ -1640,20 +1468,16 @@ int ddh_rfft_bilinear_fused(ddh_handle plan, int na, const double *const *a_h, c
         if (!has_terms[i])
             DDH_HIP(hipMemsetAsync(out_h[i], 0, (size_t)nlines * d.M * sizeof(double), as_stream(stream)));
     }
-    if (wave_path) return launch_gridwave(d, f, nlines, as_stream(stream));
-    const long npairs = (nlines + 1) / 2;
-    if ((unsigned long)npairs > 0x7fffffffUL) return fail("rfft_bilinear_fused: grid too large");
-    const size_t lds = ((size_t)d.ld * G + (size_t)tw_entries(d.N, d.twdirect)) * sizeof(double2);
-    const dim3 grid((unsigned)npairs), block(T);
     hipStream_t st = as_stream(stream);
+    if (fp.kernel == FusedKernel::gridwave2) return launch_gridwave2(fp, d, f, nlines, st);
+    if (fp.kernel == FusedKernel::gridwave) return launch_gridwave(fp, d, f, nlines, st);
+    const long npairs = (nlines + 1) / 2;
+    const dim3 grid(fp.grid), block(fp.block);
     // (four workgroups per CU instead of two were tried in round 6: 128 registers spill 350-550 bytes per lane and the
     //  kernel runs 1.6-2.9 x slower)
-    if ((long)d.N <= 3L * T) {
-        if (G == 3) hipLaunchKernelGGL((fused_rfft_bilinear_kernel<3, 3>), grid, block, lds, st, d, f, nlines, npairs);
-        else hipLaunchKernelGGL((fused_rfft_bilinear_kernel<3, 1>), grid, block, lds, st, d, f, nlines, npairs);
-    } else {
-        hipLaunchKernelGGL((fused_rfft_bilinear_kernel<6, 1>), grid, block, lds, st, d, f, nlines, npairs);
-    }
+    if (fp.PTS == 3 && G == 3) hipLaunchKernelGGL((fused_rfft_bilinear_kernel<3, 3>), grid, block, fp.lds, st, d, f, nlines, npairs);
+    else if (fp.PTS == 3) hipLaunchKernelGGL((fused_rfft_bilinear_kernel<3, 1>), grid, block, fp.lds, st, d, f, nlines, npairs);
+    else hipLaunchKernelGGL((fused_rfft_bilinear_kernel<6, 1>), grid, block, fp.lds, st, d, f, nlines, npairs);
     DDH_HIP(hipGetLastError());
     return 0;
 }

@@ -54,12 +54,6 @@ struct FftDev {
     double *dst2;          // RFFT_BWD dual output: second destination (null = single output) ...
     double dscale2;        // ... transformed with this derivative scale
     const double *dvec;    // CHEB_BWD dual output: [M] superdiagonal of the derivative operator (second pass input = dvec[k] c[k+1])
-    int spread_s, spread_c; // strided kernels: workgroup spreading over the address range (see kernel)
-    int dbg;               // timing ablations (debug): 1 skip butterfly math, 2 skip FFT passes, 4 skip unpack, 8 skip products
-    int rot;               // fused kernel: rotate the butterfly->wave assignment per workgroup
-    int twdirect;          // 1: full twiddle table in LDS (N entries) instead of the two-level table
-    int ld;                // LDS leading dimension of the FFT buffer (>= N)
-    unsigned long long *prof;   // optional phase timing (debug): [load, fft, store, count]
     unsigned xb;                // != 0: x-blocked stage layout on the INTERMEDIATE side of a strided wave transform
     unsigned xbw0, xbwn;        // xbwn != 0: the launch covers planes xbw0 .. xbw0 + xbwn of EVERY component (a window of this
                                 // rank's z planes: outer = components x xbwn), the other side holding xbwn planes per component
@@ -70,6 +64,7 @@ struct FftDev {
                                 // the rows of a line are then 8 ny doubles apart (ddh_fft_set_coeff_tiled)
     unsigned ctile_nseg;        // != 0: the coefficient rows [nx][ny] are written tile-major, ctile_nseg = ny / 8 64-byte
                                 // segments per storage row (ddh_cheb_forward_tiled; wave kernel only)
+    int ld;                     // LDS leading dimension of the FFT buffer (>= N): the workgroup kernels of ddh_fft.hip only
 };
 
 struct FftPlan : HandleBase {
@@ -92,6 +87,13 @@ struct FftPlan : HandleBase {
 constexpr int FUSED_NA = 3, FUSED_NC = 4, FUSED_NB = 12, FUSED_TERMS = 32;
 constexpr int FUSED_LOADS = FUSED_NA + FUSED_TERMS;
 constexpr int FUSED_T = 256;
+constexpr int GRIDWAVE_WAVES = 4;    // lines (wavefronts) per workgroup of the wave-per-line grid stage, both generations
+
+// largest retained wavenumber of a Fourier plan of n_grid points and n_coeff coefficients
+inline int fourier_kmax(int n_grid, int n_coeff) {
+    const int KN = (n_grid - 1) / 2, KM = (n_coeff - 1) / 2;
+    return KN < KM ? KN : KM;
+}
 
 struct FusedArgs {
     const double *src[FUSED_LOADS];   // line arrays in load order: the `a` operands first
@@ -104,5 +106,74 @@ struct FusedArgs {
     signed char ia[FUSED_TERMS];
     int na, nbatch;
 };
+
+// ------------------------------------------------------------------------------------------------
+// Which kernel a call takes (host only).  transform_plan (ddh_fftwave.hip) and fused_plan (ddh_gridwave.hip) decide it
+// once per call from the plan descriptor and the call's shape; the launchers execute the decision.  They launch nothing
+// and allocate nothing.
+// ------------------------------------------------------------------------------------------------
+
+// The sizes the wave-per-four-line-pairs transforms (ddh_wavefft.h) are instantiated for; the dispatch, the plan functions
+// and ddh_fft_wave_size are all generated from these two lists.
+// Chebyshev X(R, NL): N = 16 R grid points, M = 16 NL modes.  3/2 dealiasing of 128 / 256 modes (the configurations' radial
+// / vertical bases), no dealiasing (N = M = 64 .. 256) and factor-two padding.
+#define DDH_CHEB_WAVE_SIZES(X) X(24, 16) X(12, 8) X(16, 16) X(12, 12) X(8, 8) X(4, 4) X(16, 8) X(8, 4)
+// real Fourier with 3/2 dealiasing X(R): N = 48 R grid points, M = 32 R coefficients (128 .. 512 modes)
+#define DDH_RFFT_WAVE_SIZES(X) X(16) X(12) X(8) X(4)
+
+enum class TransformKernel {
+    cheb_wave,          // wave_cheb_kernel<kind, R, NL>: strided axis
+    rfft_wave,          // wave_rfft_kernel<kind, R>: strided axis
+    cheb_contig_wave,   // wave_cheb_contig_kernel<kind, R, NL>: contiguous axis
+    workgroup           // fft_axis_kernel<MODE, inner, tmax>: every size, either axis
+};
+struct TransformPlan {
+    const char *error;            // != nullptr: the plan's layout (xb, ctile_nseg) or the shape has no kernel
+    TransformKernel kernel;
+    int kind;                     // wave kernels: KIND / RKIND (backward 0 plain, 1 derivative / dual, 2 conversion / dual; 3 forward)
+    int R, NL;                    // wave kernels: the size's entry in the tables above (NL: Chebyshev only)
+    unsigned tpw;                 // wave kernels: tiles per wave ...
+    int wsync;                    // ... and one workgroup barrier per tile
+    unsigned tpo, ntiles;         // wave kernels: tiles per outer index (strided) and in all
+    long npairs;                  // line pairs along the paired axis
+    bool inner;                   // workgroup kernel: INNER
+    int B;                        // workgroup kernel: line pairs per workgroup (FftDev::B); TMAX follows block
+    unsigned bpo;                 // workgroup kernel: workgroups per outer index
+    unsigned grid, block;
+    size_t lds;
+    bool wave() const { return kernel != TransformKernel::workgroup; }
+};
+// second: a second output (dual entry points); deriv: derivative at load (RFFT_BWD); dvec: FftDev::dvec given;
+// aliased: the source is one of the destinations
+TransformPlan transform_plan(const FftDev &d, int mode, long outer, long inner, bool second, bool deriv, bool dvec,
+                             bool aliased);
+// the wave kernels of a plan (ddh_fftwave.hip); d carries the per-call fields (dscale, dst2, dvec)
+int launch_cheb_wave(const TransformPlan &tp, const FftDev &d, const double *src, double *dst, long inner, hipStream_t st);
+int launch_rfft_wave(const TransformPlan &tp, const FftDev &d, const double *src, double *dst, long inner, hipStream_t st);
+int launch_cheb_contig_wave(const TransformPlan &tp, const FftDev &d, const double *src, double *dst, long outer, hipStream_t st);
+
+enum class FusedKernel {
+    gridwave2,          // gw2::gridwave2_bilinear_kernel<C, NT, 4, twreg, dma>
+    gridwave,           // gw::gridwave_bilinear_kernel<C, NT, twreg>
+    workgroup           // fused_rfft_bilinear_kernel<PTS, G>
+};
+struct FusedPlan {
+    const char *error;
+    int N;                        // internal grid size: the plan's own, or the wider one (ddh_rfft_bilinear_fused)
+    FusedKernel kernel;
+    int C, NT;                    // wave kernels: N = 128 C, 64 NT coefficient pairs loaded per line
+    bool twreg, dma;              // wave kernels: twiddles in registers; second generation: operands by LDS-DMA
+    int PTS, G;                   // workgroup kernel: grid points per thread; operands per FFT batch (1 for the wave kernels)
+    long lpw;                     // wave kernels: lines per wave
+    unsigned grid, block;
+    size_t lds;
+};
+FusedPlan fused_plan(const FftDev &d, long nlines);
+// d: the descriptor of the grid size fp.N; f built with fp.G loads per batch
+int launch_gridwave(const FusedPlan &fp, const FftDev &d, const FusedArgs &f, long nlines, hipStream_t st);     // ddh_gridwave.hip
+int launch_gridwave2(const FusedPlan &fp, const FftDev &d, const FusedArgs &f, long nlines, hipStream_t st);    // ddh_gridwave2.hip
+
+// entries of the two-level twiddle table of the LDS FFT (ddh_fft.hip): W^q = hi[q >> 5] * lo[q & 31]
+__host__ __device__ __forceinline__ int tw_entries(int N) { return 32 + (N >> 5) + 1; }
 
 }  // namespace ddh

@@ -1,4 +1,5 @@
-// Strided-axis Chebyshev transforms, one wavefront per four line pairs (ddh_wavefft.h): kernels and launch.
+// Strided-axis Chebyshev transforms, one wavefront per four line pairs (ddh_wavefft.h): kernels and launch; transform_plan,
+// the one place that decides which kernel a transform call takes.
 //
 // A workgroup is 8 independent wavefronts that share the read-only tables in LDS (twiddles, half-angle factors,
 // conversion bands / back-substitution table / derivative vector) and nothing else: no workgroup barrier after the
@@ -148,31 +149,14 @@ wave_cheb_kernel(FftDev p, WaveArgs a) {
     }
 }
 
-template <int KIND, int R, int NL, int CH>
-static int launch_wave_cheb(const FftDev &d, const WaveArgs &a, unsigned nwg, hipStream_t st) {
-    const int N = 16 * R;
-    constexpr bool FWD = (KIND == 3);
-    const int nd = FWD ? d.nbands * d.M : 3 * d.M;
-    const size_t lds = (size_t)2 * N * sizeof(double2) + (size_t)((nd + 1) & ~1) * sizeof(double) +
-                       (size_t)WV_WAVES * wf::ChebWaveLds<R, NL, CH>::size * sizeof(double2);
-    if (lds > 160 * 1024) return 1;
-    auto kern = wave_cheb_kernel<KIND, R, NL, CH>;
-    if (lds > 64 * 1024)
-        DDH_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(nwg), dim3(64 * WV_WAVES), lds, st, d, a);
+template <int KIND, int R, int NL>
+static int launch_wave_cheb(const TransformPlan &tp, const FftDev &d, const WaveArgs &a, hipStream_t st) {
+    auto kern = wave_cheb_kernel<KIND, R, NL, wf::WaveCH<R>::ch>;
+    if (tp.lds > 64 * 1024)
+        DDH_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tp.lds));
+    hipLaunchKernelGGL(kern, dim3(tp.grid), dim3(tp.block), tp.lds, st, d, a);
     DDH_HIP(hipGetLastError());
     return 0;
-}
-
-template <int R, int NL>
-static int launch_wave_cheb_kind(int kind, const FftDev &d, const WaveArgs &a, unsigned nwg, hipStream_t st) {
-    constexpr int CH = wf::WaveCH<R>::ch;
-    switch (kind) {
-        case 3: return launch_wave_cheb<3, R, NL, CH>(d, a, nwg, st);
-        case 2: return launch_wave_cheb<2, R, NL, CH>(d, a, nwg, st);
-        case 1: return launch_wave_cheb<1, R, NL, CH>(d, a, nwg, st);
-        default: return launch_wave_cheb<0, R, NL, CH>(d, a, nwg, st);
-    }
 }
 
 // ---- Chebyshev along the CONTIGUOUS axis (the shell's radial transforms: [lines][192] <-> [lines][128]) ------------------
@@ -298,76 +282,14 @@ wave_cheb_contig_kernel(FftDev p, ContigArgs a) {
     }
 }
 
-template <int KIND, int R, int NL, int CH>
-static int launch_wave_cheb_contig(const FftDev &d, const ContigArgs &a, unsigned nwg, hipStream_t st) {
-    const int N = 16 * R;
-    constexpr bool FWD = (KIND == 3);
-    const int nd = FWD ? d.nbands * d.M : 3 * d.M;
-    const size_t lds = (size_t)2 * N * sizeof(double2) + (size_t)((nd + 1) & ~1) * sizeof(double) +
-                       (size_t)WC_WAVES * ChebContigLds<R, NL, CH>::size * sizeof(double2);
-    if (lds > 160 * 1024) return 1;
-    auto kern = wave_cheb_contig_kernel<KIND, R, NL, CH>;
-    if (lds > 64 * 1024)
-        DDH_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(nwg), dim3(64 * WC_WAVES), lds, st, d, a);
+template <int KIND, int R, int NL>
+static int launch_wave_cheb_contig(const TransformPlan &tp, const FftDev &d, const ContigArgs &a, hipStream_t st) {
+    auto kern = wave_cheb_contig_kernel<KIND, R, NL, wf::WaveCH<R>::ch>;
+    if (tp.lds > 64 * 1024)
+        DDH_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tp.lds));
+    hipLaunchKernelGGL(kern, dim3(tp.grid), dim3(tp.block), tp.lds, st, d, a);
     DDH_HIP(hipGetLastError());
     return 0;
-}
-
-template <int R, int NL>
-static int launch_wave_cheb_contig_kind(int kind, const FftDev &d, const ContigArgs &a, unsigned nwg, hipStream_t st) {
-    constexpr int CH = wf::WaveCH<R>::ch;
-    switch (kind) {
-        case 3: return launch_wave_cheb_contig<3, R, NL, CH>(d, a, nwg, st);
-        case 2: return launch_wave_cheb_contig<2, R, NL, CH>(d, a, nwg, st);
-        case 1: return launch_wave_cheb_contig<1, R, NL, CH>(d, a, nwg, st);
-        default: return launch_wave_cheb_contig<0, R, NL, CH>(d, a, nwg, st);
-    }
-}
-
-// The (grid, coefficient) sizes the wave Chebyshev kernels are instantiated for: N = 16 R grid points, M = 16 NL modes.
-// 3/2 dealiasing of 128 / 256 modes (the configurations' radial / vertical bases), no dealiasing (N = M = 64 .. 256) and
-// factor-two padding; everything else takes the workgroup-per-tile kernel of ddh_fft.hip.
-#define DDH_CHEB_WAVE_SIZES(X) X(24, 16) X(12, 8) X(16, 16) X(12, 12) X(8, 8) X(4, 4) X(16, 8) X(8, 4)
-
-// 0 = launched, 1 = shape not covered
-int wave_contig_try(int mode, const FftDev &d, const double *src, double *dst, long outer, double *dst2, hipStream_t st) {
-    static const int on = getenv("DDH_CHEB_CONTIG_WAVE") ? atoi(getenv("DDH_CHEB_CONTIG_WAVE")) : 1;
-    if (!on || d.dbg || d.prof || d.xb || d.ctile_nseg) return 1;
-    if (mode != CHEB_FWD && mode != CHEB_BWD) return 1;
-    if ((outer & 1) || outer < 2) return 1;
-    if (src == dst || src == dst2) return 1;
-    ContigArgs a;
-    a.src = src;
-    a.dst = dst;
-    a.dst2 = dst2;
-    a.nlines = outer;
-    const unsigned long ntiles = ((unsigned long)outer + 7) / 8;
-    if (ntiles > 0x7fffffffUL) return 1;
-    a.ntiles = (unsigned)ntiles;
-    a.kind = 0;
-    if (mode == CHEB_BWD) {
-        if (dst2) {
-            if (!(d.bsub && d.bsub_order == 1 && (d.gcd_off == 1 || d.gcd_off == 2) && d.dvec)) return 1;
-            a.kind = 1;
-        } else if (d.nbands > 0) {
-            if (!(d.bsub && d.bsub_order == 1 && (d.gcd_off == 1 || d.gcd_off == 2))) return 1;
-            a.kind = 2;
-        }
-    } else if (dst2) {
-        return 1;
-    }
-    static const int env_tpw = getenv("DDH_CHEB_CONTIG_TPW") ? atoi(getenv("DDH_CHEB_CONTIG_TPW")) : 0;
-    unsigned tpw = (unsigned)(env_tpw > 0 ? env_tpw : 4);
-    while (tpw > 1 && ntiles / ((unsigned long)tpw * WC_WAVES) < 2048) tpw /= 2;
-    a.tpw = tpw;
-    const unsigned nwg = (unsigned)((ntiles + (unsigned long)tpw * WC_WAVES - 1) / ((unsigned long)tpw * WC_WAVES));
-    const int kind = (mode == CHEB_FWD) ? 3 : a.kind;
-#define DDH_X(RV, NLV) \
-    if (d.N == 16 * RV && d.M == 16 * NLV) return launch_wave_cheb_contig_kind<RV, NLV>(kind, d, a, nwg, st);
-    DDH_CHEB_WAVE_SIZES(DDH_X)
-#undef DDH_X
-    return 1;
 }
 
 // ---- real Fourier, 3/2 dealiasing (N = 48 R, M = 32 R): RKIND 0 backward, 1 backward differentiated, 2 backward dual
@@ -423,124 +345,246 @@ wave_rfft_kernel(FftDev p, WaveArgs a) {
 }
 
 template <int RKIND, int R>
-static int launch_wave_rfft(const FftDev &d, const WaveArgs &a, unsigned nwg, hipStream_t st) {
-    const size_t lds = ((size_t)48 * R + (size_t)WR_WAVES * wf::RfftWaveLds<R>::size) * sizeof(double2);
-    if (lds > 160 * 1024) return 1;
+static int launch_wave_rfft(const TransformPlan &tp, const FftDev &d, const WaveArgs &a, hipStream_t st) {
     auto kern = wave_rfft_kernel<RKIND, R>;
-    if (lds > 64 * 1024)
-        DDH_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(nwg), dim3(64 * WR_WAVES), lds, st, d, a);
+    if (tp.lds > 64 * 1024)
+        DDH_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tp.lds));
+    hipLaunchKernelGGL(kern, dim3(tp.grid), dim3(tp.block), tp.lds, st, d, a);
     DDH_HIP(hipGetLastError());
     return 0;
 }
 
-template <int R>
-static int launch_wave_rfft_kind(int rk, const FftDev &d, const WaveArgs &a, unsigned nwg, hipStream_t st) {
-    switch (rk) {
-        case 3: return launch_wave_rfft<3, R>(d, a, nwg, st);
-        case 2: return launch_wave_rfft<2, R>(d, a, nwg, st);
-        case 1: return launch_wave_rfft<1, R>(d, a, nwg, st);
-        default: return launch_wave_rfft<0, R>(d, a, nwg, st);
+// ---- which kernel a transform takes -------------------------------------------------------------------------------------
+// A size's entry in DDH_CHEB_WAVE_SIZES / DDH_RFFT_WAVE_SIZES and the LDS its kernels need per wave (double2)
+struct WaveSize {
+    int R, NL;
+    size_t strided, contig;
+};
+static bool wave_size(int kind, int N, int M, WaveSize &ws) {
+#define DDH_X(RV, NLV)                                                                             \
+    if (kind == K_CHEB && N == 16 * RV && M == 16 * NLV) {                                         \
+        ws = {RV, NLV, (size_t)wf::ChebWaveLds<RV, NLV, wf::WaveCH<RV>::ch>::size,                  \
+              (size_t)ChebContigLds<RV, NLV, wf::WaveCH<RV>::ch>::size};                           \
+        return true;                                                                               \
     }
+    DDH_CHEB_WAVE_SIZES(DDH_X)
+#undef DDH_X
+#define DDH_X(RV)                                                                                  \
+    if (kind == K_RFFT && N == 48 * RV && M == 32 * RV) {                                          \
+        ws = {RV, 0, (size_t)wf::RfftWaveLds<RV>::size, 0};                                        \
+        return true;                                                                               \
+    }
+    DDH_RFFT_WAVE_SIZES(DDH_X)
+#undef DDH_X
+    return false;
 }
 
-// Returns 0 when the transform was launched here, 1 when the shape is not covered (the caller then uses the
-// workgroup-per-tile kernel of ddh_fft.hip), < 0 on error.
-int wave_axis_try(int mode, const FftDev &d, const double *src, double *dst, long outer, long inner, double *dst2,
-                  const double *dvec, double dscale, double dscale2, hipStream_t st) {
-    static const int mask = getenv("DDH_FFT_WAVE") ? atoi(getenv("DDH_FFT_WAVE")) : 3;     // bit 0: Chebyshev, bit 1: real FFT
-    // tiles per wave / per-tile workgroup sync: measured per kernel at 3 x 256 x 512^2 and 1152 x 512 x 512
-    // (tools/bench_strided.py, profiles/r3_strided_sweep.txt); the environment overrides all of them
-    static const int env_tpw = getenv("DDH_FFT_TPW") ? atoi(getenv("DDH_FFT_TPW")) : 0;
-    static const int env_wsync = getenv("DDH_FFT_WSYNC") ? atoi(getenv("DDH_FFT_WSYNC")) : -1;
-    if (d.dbg || d.prof) return 1;
-    if (d.xb) {
-        // x-blocked stage layout: shapes it is defined for (the caller falls back to an error, never to another layout)
-        if (mode == CHEB_FWD || mode == CHEB_BWD) {
-            if ((d.xb & 7) || inner % d.xb || (inner / d.xb) % 64) return 1;
-        } else if (mode == RFFT_FWD || mode == RFFT_BWD) {
+TransformPlan transform_plan(const FftDev &d, int mode, long outer, long inner, bool second, bool deriv, bool dvec,
+                             bool aliased) {
+    // A/B and fallback selectors (read here and nowhere else).  DDH_FFT_WAVE: bit 0 Chebyshev, bit 1 real FFT on the strided
+    // wave kernels; DDH_CHEB_CONTIG_WAVE=0: contiguous Chebyshev lines on the workgroup kernel
+    static const int mask = getenv("DDH_FFT_WAVE") ? atoi(getenv("DDH_FFT_WAVE")) : 3;
+    static const int contig_on = getenv("DDH_CHEB_CONTIG_WAVE") ? atoi(getenv("DDH_CHEB_CONTIG_WAVE")) : 1;
+    TransformPlan tp{};
+    const bool cheb = (mode == CHEB_FWD || mode == CHEB_BWD), rfft = (mode == RFFT_FWD || mode == RFFT_BWD);
+    const bool cfft = !cheb && !rfft, strided = inner > 1;
+    const int N = d.N;
+    WaveSize ws{};
+    bool wave_ok = !cfft && wave_size(cheb ? K_CHEB : K_RFFT, N, d.M, ws);
+    tp.R = ws.R;
+    tp.NL = ws.NL;
+    // the variant of the size's wave kernel; the conversion solve of the wave kernels takes first-order chains of stride 1 or 2
+    const bool chain_ok = d.bsub && d.bsub_order == 1 && (d.gcd_off == 1 || d.gcd_off == 2);
+    if (mode == CHEB_FWD || mode == RFFT_FWD) {
+        tp.kind = 3;
+    } else if (mode == CHEB_BWD && second) {
+        tp.kind = 1;
+        wave_ok = wave_ok && chain_ok && dvec;
+    } else if (mode == CHEB_BWD && d.nbands > 0) {
+        tp.kind = 2;
+        wave_ok = wave_ok && chain_ok;
+    } else if (mode == RFFT_BWD) {
+        tp.kind = second ? 2 : (deriv ? 1 : 0);
+        wave_ok = wave_ok && !(second && deriv);     // the dual entry point transforms plainly into dst
+    }
+    if (rfft) wave_ok = wave_ok && d.K == d.M / 2 - 1;
+    // LDS of the Chebyshev wave kernels: twiddles, half-angle factors, the bands / back-substitution + derivative tables
+    const size_t cheb_tabs = (size_t)2 * N * sizeof(double2) + (size_t)(((mode == CHEB_FWD ? d.nbands * d.M : 3 * d.M) + 1) & ~1) * sizeof(double);
+
+    if (wave_ok && strided && (mask & (cheb ? 1 : 2)) && !(inner & 1)) {
+        // the plan's layouts: shapes they are defined for
+        bool layout_ok = true;
+        if (d.xb && cheb) {
+            layout_ok = !((d.xb & 7) || inner % d.xb || (inner / d.xb) % 64);
+        } else if (d.xb) {
             const unsigned long B = d.xbB ? d.xbB : 64UL;
-            if (!(B == 64 || B == 128 || B == 256)) return 1;
             // (outer: whole components of gz planes each, or of the xbwn planes of a window)
-            if (d.xbwn && (d.xbw0 + d.xbwn > d.xb)) return 1;
-            if (outer % (d.xbwn ? d.xbwn : d.xb) || d.M % B || (unsigned long)d.xb * B * (unsigned long)inner * 8UL * (unsigned long)(d.M / B) >= 0xffffffffUL) return 1;
-        } else {
-            return 1;
+            layout_ok = (B == 64 || B == 128 || B == 256) && !(d.xbwn && (d.xbw0 + d.xbwn > d.xb)) &&
+                        !(outer % (d.xbwn ? d.xbwn : d.xb) || d.M % B ||
+                          (unsigned long)d.xb * B * (unsigned long)inner * 8UL * (unsigned long)(d.M / B) >= 0xffffffffUL);
+        }
+        if (d.ctile_nseg && (!cheb || inner % (8L * d.ctile_nseg) || (inner / (8L * d.ctile_nseg)) % 8)) layout_ok = false;
+        const long npairs = inner / 2, tpo = (npairs + 3) / 4;
+        const unsigned long ntiles = (unsigned long)tpo * (unsigned long)outer;
+        const unsigned long wpg = rfft ? WR_WAVES : WV_WAVES;
+        const size_t lds = rfft ? ((size_t)N + wpg * ws.strided) * sizeof(double2) : cheb_tabs + wpg * ws.strided * sizeof(double2);
+        if (layout_ok && ntiles <= 0x7fffffffUL && lds <= 160 * 1024 &&
+            (unsigned long)N * (unsigned long)inner * 8UL < 0xffffffffUL) {     // 32-bit row offsets inside a tile
+            tp.kernel = cheb ? TransformKernel::cheb_wave : TransformKernel::rfft_wave;
+            tp.npairs = npairs;
+            tp.tpo = (unsigned)tpo;
+            tp.ntiles = (unsigned)ntiles;
+            // tiles per wave / per-tile workgroup sync: measured per kernel at 3 x 256 x 512^2 and 1152 x 512 x 512
+            // (tools/bench_strided.py, profiles/archive/r3_strided_sweep.txt)
+            unsigned tpw = 1;
+            if (mode == CHEB_FWD) {
+                tpw = 4;
+                tp.wsync = 1;
+            } else if (mode == CHEB_BWD && tp.kind != 1) {
+                tpw = 2;
+            }
+            while (tpw > 1 && ntiles / (tpw * wpg) < 1024) tpw /= 2;   // several rounds of workgroups
+            tp.tpw = tpw;
+            tp.grid = (unsigned)((ntiles + tpw * wpg - 1) / (tpw * wpg));
+            tp.block = (unsigned)(64 * wpg);
+            tp.lds = lds;
+            return tp;
         }
     }
-    if (d.ctile_nseg && ((mode != CHEB_FWD && mode != CHEB_BWD) || inner % (8L * d.ctile_nseg) || (inner / (8L * d.ctile_nseg)) % 8)) return 1;
-    const bool cheb = (mode == CHEB_FWD || mode == CHEB_BWD), rfft = (mode == RFFT_FWD || mode == RFFT_BWD);
-    if (!cheb && !rfft) return 1;
-    if ((cheb && !(mask & 1)) || (rfft && !(mask & 2))) return 1;
-    if (inner < 2 || (inner & 1)) return 1;
-    if (cheb) {
-        bool have = false;
-#define DDH_X(RV, NLV) have = have || (d.N == 16 * RV && d.M == 16 * NLV);
-        DDH_CHEB_WAVE_SIZES(DDH_X)
-#undef DDH_X
-        if (!have) return 1;
+    if (wave_ok && !strided && cheb && contig_on && !d.xb && !d.ctile_nseg && !(outer & 1) && outer >= 2 && !aliased) {
+        const unsigned long ntiles = ((unsigned long)outer + 7) / 8;
+        const size_t lds = cheb_tabs + (size_t)WC_WAVES * ws.contig * sizeof(double2);
+        if (ntiles <= 0x7fffffffUL && lds <= 160 * 1024) {
+            tp.kernel = TransformKernel::cheb_contig_wave;
+            tp.ntiles = (unsigned)ntiles;
+            unsigned long tpw = 4;
+            while (tpw > 1 && ntiles / (tpw * WC_WAVES) < 2048) tpw /= 2;   // several rounds of workgroups
+            tp.tpw = (unsigned)tpw;
+            tp.grid = (unsigned)((ntiles + tpw * WC_WAVES - 1) / (tpw * WC_WAVES));
+            tp.block = 64 * WC_WAVES;
+            tp.lds = lds;
+            return tp;
+        }
     }
-    // real FFT with 3/2 padding: N = 48 R, M = 32 R for the instantiated R = 4, 8, 12, 16 (128 .. 512 modes)
-    if (rfft && !(d.N % 48 == 0 && 3 * d.M == 2 * d.N && (d.N == 192 || d.N == 384 || d.N == 576 || d.N == 768))) return 1;
-    if (rfft && d.K != d.M / 2 - 1) return 1;
-    const long npairs = inner / 2;
-    const long tpo = (npairs + 3) / 4;
-    const unsigned long ntiles = (unsigned long)tpo * (unsigned long)outer;
-    if (ntiles > 0x7fffffffUL) return 1;
-    if ((unsigned long)d.N * (unsigned long)inner * 8UL >= 0xffffffffUL) return 1;     // 32-bit row offsets inside a tile
+
+    // the workgroup-per-tile kernel of ddh_fft.hip: every size, natural layouts only
+    tp.kernel = TransformKernel::workgroup;
+    if (d.xb && strided) {
+        tp.error = "x-blocked stage layout (ddh_fft_set_stage_layout): only the strided-axis wave kernels at their instantiated "
+                   "sizes read / write it, and this transform has none";
+        return tp;
+    }
+    if (d.ctile_nseg) {
+        tp.error = "tile-major coefficient rows (ddh_cheb_forward_tiled, ddh_fft_set_coeff_tiled): only the strided-axis "
+                   "Chebyshev wave kernels at their instantiated sizes read / write that layout";
+        return tp;
+    }
+    tp.inner = strided;
+    if (cfft)
+        tp.npairs = strided ? inner : outer;
+    else
+        tp.npairs = strided ? (inner + 1) / 2 : (outer + 1) / 2;
+    // lines per workgroup: 128 B of contiguous data per row when strided; bounded by LDS (<= 64 KiB so that at least two
+    // workgroups share a CU) and by 12 staged values per thread.
+    const size_t per_line = (size_t)d.ld * sizeof(double2);
+    int B = strided ? 8 : 4;
+    if (!strided) {
+        // contiguous SHORT lines (the shell's radial transforms: 192 <- 128): 4 line pairs are a tile of a few KiB, the
+        // workgroup's fixed costs (twiddle tables, barriers) dominate -- up to 16 pairs while a thread keeps <= 12 items
+        while (B < 16 && (long)N * (2 * B) <= 12L * 256) B *= 2;
+    }
+    while (B > 1 && per_line * B > 64 * 1024) B /= 2;
+    if ((long)B > tp.npairs) B = (int)tp.npairs;
+    if (per_line * B > 160 * 1024) {
+        tp.error = "transform: axis too long for the LDS kernel";
+        return tp;
+    }
+    int T = 256;
+    while ((long)N * B > 12L * T && T < 1024) T *= 2;
+    if ((long)N * B > 12L * T) {
+        tp.error = "transform: axis too long for the LDS kernel (registers)";
+        return tp;
+    }
+    tp.B = B;
+    tp.bpo = (unsigned)((tp.npairs + B - 1) / B);
+    const unsigned long nblocks = strided ? (unsigned long)tp.bpo * (unsigned long)outer : tp.bpo;
+    if (nblocks > 0x7fffffffUL) {
+        tp.error = "transform: grid too large";
+        return tp;
+    }
+    tp.grid = (unsigned)nblocks;
+    tp.block = (unsigned)T;
+    tp.lds = per_line * B + (size_t)tw_entries(N) * sizeof(double2);
+    return tp;
+}
+
+static WaveArgs wave_args(const TransformPlan &tp, const FftDev &d, const double *src, double *dst, long inner) {
     WaveArgs a;
     a.src = src;
     a.dst = dst;
-    a.dst2 = dst2;
+    a.dst2 = d.dst2;
     a.inner = inner;
-    a.npairs = npairs;
-    a.fd_tpo.set((unsigned)tpo);
-    a.ntiles = (unsigned)ntiles;
-    a.kind = 0;
-    a.wsync = 0;
-    FftDev dd = d;
-    dd.dvec = dvec;
-    dd.dscale = dscale;
-    dd.dscale2 = dscale2;
-    if (mode == CHEB_BWD) {
-        if (dst2) {
-            if (!(d.bsub && d.bsub_order == 1 && (d.gcd_off == 1 || d.gcd_off == 2) && dvec)) return 1;
-            a.kind = 1;
-        } else if (d.nbands > 0) {
-            if (!(d.bsub && d.bsub_order == 1 && (d.gcd_off == 1 || d.gcd_off == 2))) return 1;
-            a.kind = 2;
-        }
-    }
-    int def_tpw = 1, def_wsync = 0;
-    if (mode == CHEB_FWD) {
-        def_tpw = 4;
-        def_wsync = 1;
-    } else if (mode == CHEB_BWD && a.kind != 1) {
-        def_tpw = 2;
-    }
-    a.wsync = env_wsync >= 0 ? env_wsync : def_wsync;
-    unsigned tpw = (unsigned)(env_tpw > 0 ? env_tpw : def_tpw);
-    const unsigned long wpg = rfft ? WR_WAVES : WV_WAVES;
-    while (tpw > 1 && ntiles / ((unsigned long)tpw * wpg) < 1024) tpw /= 2;   // several rounds of workgroups
-    a.tpw = tpw;
-    const unsigned nwg = (unsigned)((ntiles + (unsigned long)tpw * wpg - 1) / ((unsigned long)tpw * wpg));
-    if (rfft) {
-        if (dst2 && dscale != 0.0) return 1;                    // the dual entry point transforms plainly into dst
-        const int rk = (mode == RFFT_FWD) ? 3 : (dst2 ? 2 : (dscale != 0.0 ? 1 : 0));
-        switch (d.N / 48) {
-            case 16: return launch_wave_rfft_kind<16>(rk, dd, a, nwg, st);
-            case 12: return launch_wave_rfft_kind<12>(rk, dd, a, nwg, st);
-            case 8: return launch_wave_rfft_kind<8>(rk, dd, a, nwg, st);
-            case 4: return launch_wave_rfft_kind<4>(rk, dd, a, nwg, st);
-        }
-        return 1;
-    }
-    const int ck = (mode == CHEB_FWD) ? 3 : a.kind;
-#define DDH_X(RV, NLV) \
-    if (d.N == 16 * RV && d.M == 16 * NLV) return launch_wave_cheb_kind<RV, NLV>(ck, dd, a, nwg, st);
-    DDH_CHEB_WAVE_SIZES(DDH_X)
-#undef DDH_X
-    return 1;
+    a.npairs = tp.npairs;
+    a.fd_tpo.set(tp.tpo);
+    a.ntiles = tp.ntiles;
+    a.tpw = tp.tpw;
+    a.kind = tp.kind == 3 ? 0 : tp.kind;
+    a.wsync = tp.wsync;
+    return a;
 }
 
+// the template instance of a plan: KIND / RKIND x the size tables
+#define DDH_KIND_SWITCH(FN, ...)                                       \
+    switch (tp.kind) {                                                 \
+        case 3: return FN<3, __VA_ARGS__>(tp, d, a, st);               \
+        case 2: return FN<2, __VA_ARGS__>(tp, d, a, st);               \
+        case 1: return FN<1, __VA_ARGS__>(tp, d, a, st);               \
+        default: return FN<0, __VA_ARGS__>(tp, d, a, st);              \
+    }
+
+int launch_cheb_wave(const TransformPlan &tp, const FftDev &d, const double *src, double *dst, long inner, hipStream_t st) {
+    const WaveArgs a = wave_args(tp, d, src, dst, inner);
+#define DDH_X(RV, NLV) \
+    if (tp.R == RV && tp.NL == NLV) DDH_KIND_SWITCH(launch_wave_cheb, RV, NLV)
+    DDH_CHEB_WAVE_SIZES(DDH_X)
+#undef DDH_X
+    return fail("transform: no Chebyshev wave kernel of this size");
+}
+
+int launch_rfft_wave(const TransformPlan &tp, const FftDev &d, const double *src, double *dst, long inner, hipStream_t st) {
+    const WaveArgs a = wave_args(tp, d, src, dst, inner);
+#define DDH_X(RV) \
+    if (tp.R == RV) DDH_KIND_SWITCH(launch_wave_rfft, RV)
+    DDH_RFFT_WAVE_SIZES(DDH_X)
+#undef DDH_X
+    return fail("transform: no real-FFT wave kernel of this size");
+}
+
+int launch_cheb_contig_wave(const TransformPlan &tp, const FftDev &d, const double *src, double *dst, long outer, hipStream_t st) {
+    ContigArgs a;
+    a.src = src;
+    a.dst = dst;
+    a.dst2 = d.dst2;
+    a.nlines = outer;
+    a.ntiles = tp.ntiles;
+    a.tpw = tp.tpw;
+    a.kind = tp.kind == 3 ? 0 : tp.kind;
+#define DDH_X(RV, NLV) \
+    if (tp.R == RV && tp.NL == NLV) DDH_KIND_SWITCH(launch_wave_cheb_contig, RV, NLV)
+    DDH_CHEB_WAVE_SIZES(DDH_X)
+#undef DDH_X
+    return fail("transform: no Chebyshev wave kernel of this size");
+}
+#undef DDH_KIND_SWITCH
+
 }  // namespace ddh
+
+using namespace ddh;
+
+extern "C" int ddh_fft_wave_size(int kind, int n_grid, int n_coeff, int *covered) {
+    if (!covered) return fail("ddh_fft_wave_size: null pointer");
+    if (kind != K_RFFT && kind != K_CHEB) return fail("ddh_fft_wave_size: kind 0 (real FFT) or 1 (Chebyshev)");
+    WaveSize ws;
+    *covered = wave_size(kind, n_grid, n_coeff, ws) ? 1 : 0;
+    return 0;
+}

@@ -18,6 +18,7 @@
 // Exchange layouts keep every ds_read_b128 lane-contiguous (conflict free) and pad the strided side
 // (the writes, whose cost is the data transfer to the LDS, tolerate the residual 2-way conflicts).
 #include "ddh_fft_dev.h"
+#include "ddh_gridwave2.h"       // G2<C>: the LDS of the second generation, for fused_plan
 
 #include <algorithm>
 #include <cstdlib>
@@ -157,7 +158,7 @@ __device__ __forceinline__ void build_z_from_lds(double dscale, const double2 *w
 // Staged pairs -> LDS in natural order (zeros beyond the loaded range), then the pre-processing
 template <int C, int NT>
 __device__ __forceinline__ void build_z(const LineLoads<NT> &ld, double dscale, double2 *wb, const double2 *tw,
-                                        int lane, double2 *v, int dbg = 0) {
+                                        int lane, double2 *v) {
     using G = GW<C>;
     // (blocks beyond the largest index the pruned pre-processing reads are not written: an LDS store costs 13 cycles)
     constexpr int KM = 64 * NT - 1;
@@ -168,13 +169,8 @@ __device__ __forceinline__ void build_z(const LineLoads<NT> &ld, double dscale, 
     constexpr int TWR = (RMAX / 64 + 1) < C ? (RMAX / 64 + 1) : C;
 #pragma unroll
     for (int t = 0; t < TWR; ++t)
-        if (!(dbg & 64)) wb[lane + 64 * t] = (t < NT) ? ld.x[t] : make_double2(0.0, 0.0);
+        wb[lane + 64 * t] = (t < NT) ? ld.x[t] : make_double2(0.0, 0.0);
     wave_sync();
-    if (dbg & 128) {                                       // timing ablation: no LDS reads
-#pragma unroll
-        for (int a = 0; a < 8; ++a) v[a] = make_double2(ld.x[a % NT].x + a, ld.x[a % NT].y * dscale);
-        return;
-    }
     if (lane < G::NB) {
         if (dscale != 0.0) build_z_from_lds<C, NT, true>(dscale, wb, tw, lane, v);     // wave-uniform branch
         else build_z_from_lds<C, NT, false>(dscale, wb, tw, lane, v);
@@ -188,52 +184,49 @@ __device__ __forceinline__ void build_z(const LineLoads<NT> &ld, double dscale, 
 // by the LDS pipe and runs at 2 waves per SIMD whatever it does with the 60 registers)
 template <int C, bool TWREG = false>
 __device__ __forceinline__ void backward_line(double2 *v, double2 *wb, const double2 *tw, int lane, double2 *g,
-                                              int dbg, const double2 *t1r = nullptr, const double2 *t2r = nullptr) {
+                                              const double2 *t1r = nullptr, const double2 *t2r = nullptr) {
     using G = GW<C>;
     const int b1 = lane / C, c1 = lane - b1 * C;     // pass 1: butterfly j = lane = b*C + c; pass 2: lr = n1*C + c
     if (lane < G::NB) {
-        if (!(dbg & 1)) butterfly<8>(v, +1);
+        butterfly<8>(v, +1);
         // twiddle W64^(n1 b), then exchange 1: [b][n1*C + c]
-        if (!(dbg & 64)) wb[b1 * G::S1 + c1] = v[0];
+        wb[b1 * G::S1 + c1] = v[0];
 #pragma unroll
         for (int n1 = 1; n1 < 8; ++n1) {
             const double2 w = conj2(TWREG ? t1r[n1 - 1] : tw[G::T_1 + n1 * 8 + b1]);
-            if (dbg & 64) v[n1] = cmul(v[n1], w); else
             wb[b1 * G::S1 + n1 * C + c1] = cmul(v[n1], w);
         }
     }
     wave_sync();
     if (lane < G::NB) {
 #pragma unroll
-        for (int b = 0; b < 8; ++b) if (!(dbg & 128)) v[b] = wb[b * G::S1 + lane];
-        if (!(dbg & 1)) butterfly<8>(v, +1);
+        for (int b = 0; b < 8; ++b) v[b] = wb[b * G::S1 + lane];
+        butterfly<8>(v, +1);
         // twiddle omega^((n1 + 8 n2) c), omega = exp(2 pi i / H); exchange 2: [c][n2 + 8 n1]
         const int n1 = b1, c = c1;
 #pragma unroll
         for (int n2 = 0; n2 < 8; ++n2) {
             const double2 w = conj2(TWREG ? t2r[n2] : tw[G::T_2 + n2 * G::STR + lane]);
-            if (dbg & 64) v[n2] = cmul(v[n2], w); else
             wb[c * G::S2 + n2 + 8 * n1] = cmul(v[n2], w);
         }
     }
     wave_sync();
 #pragma unroll
-    for (int c = 0; c < C; ++c) g[c] = (dbg & 128) ? v[c] : wb[c * G::S2 + lane];
-    if (!(dbg & 1)) butterfly<C>(g, +1);
+    for (int c = 0; c < C; ++c) g[c] = wb[c * G::S2 + lane];
+    butterfly<C>(g, +1);
 }
 
 // forward transform of the grid values g (same lane/register map) and store of the coefficient line
 template <int C, bool TWREG = false>
 __device__ __forceinline__ void forward_line(double2 *g, double2 *wb, const double2 *tw, int lane, double *dst,
-                                             int M, int K, int dbg, const double2 *t1r = nullptr) {
+                                             int M, int K, const double2 *t1r = nullptr) {
     using G = GW<C>;
     const int n2L = lane & 7, n1L = lane >> 3;
-    if (!(dbg & 1)) butterfly<C>(g, -1);
+    butterfly<C>(g, -1);
     {
 #pragma unroll
         for (int c = 0; c < C; ++c) {
             const double2 w = tw[G::T_2 + n2L * G::STR + n1L * C + c];
-            if (dbg & 64) g[c] = (c == 0) ? g[0] : cmul(g[c], w); else
             wb[n2L * G::S2F + n1L * C + c] = (c == 0) ? g[0] : cmul(g[c], w);
         }
     }
@@ -242,24 +235,23 @@ __device__ __forceinline__ void forward_line(double2 *g, double2 *wb, const doub
     double2 v[8];
     if (lane < G::NB) {
 #pragma unroll
-        for (int n2 = 0; n2 < 8; ++n2) v[n2] = (dbg & 128) ? g[n2 % C] : wb[n2 * G::S2F + lane];
-        if (!(dbg & 1)) butterfly<8>(v, -1);
+        for (int n2 = 0; n2 < 8; ++n2) v[n2] = wb[n2 * G::S2F + lane];
+        butterfly<8>(v, -1);
         // twiddle conj W64^(n1 b); exchange 1: [n1][b*C + c]
-        if (!(dbg & 64)) wb[n1 * G::S1 + c1] = v[0];
+        wb[n1 * G::S1 + c1] = v[0];
 #pragma unroll
         for (int b = 1; b < 8; ++b) {
             const double2 w = TWREG ? t1r[b - 1] : tw[G::T_1 + b * 8 + n1];       // (the table is symmetric)
-            if (dbg & 64) v[b] = cmul(v[b], w); else
             wb[n1 * G::S1 + b * C + c1] = cmul(v[b], w);
         }
     }
     wave_sync();
     if (lane < G::NB) {
 #pragma unroll
-        for (int q = 0; q < 8; ++q) if (!(dbg & 128)) v[q] = wb[q * G::S1 + lane];
-        if (!(dbg & 1)) butterfly<8>(v, -1);
+        for (int q = 0; q < 8; ++q) v[q] = wb[q * G::S1 + lane];
+        butterfly<8>(v, -1);
 #pragma unroll
-        for (int a = 0; a < 8; ++a) if (!(dbg & 64)) wb[lane + G::NB * a] = v[a];     // natural order Zf[k]
+        for (int a = 0; a < 8; ++a) wb[lane + G::NB * a] = v[a];     // natural order Zf[k]
     }
     wave_sync();
     // Y[k] = E + exp(-2 pi i k / N) O,  E = (Zf[k] + conj Zf[H-k]) / 2,  O = -i (Zf[k] - conj Zf[H-k]) / 2
@@ -274,7 +266,7 @@ __device__ __forceinline__ void forward_line(double2 *g, double2 *wb, const doub
                 const double2 z = wb[0];
                 out.x = (z.x + z.y) * invN;
             } else if (k <= K) {
-                const double2 z = (dbg & 128) ? v[t] : wb[k], zm = (dbg & 128) ? v[7 - t] : wb[G::H - k];
+                const double2 z = wb[k], zm = wb[G::H - k];
                 const double2 E = make_double2(0.5 * (z.x + zm.x), 0.5 * (z.y - zm.y));
                 const double2 D = make_double2(0.5 * (z.x - zm.x), 0.5 * (z.y + zm.y));
                 const double2 O = make_double2(D.y, -D.x);
@@ -282,19 +274,19 @@ __device__ __forceinline__ void forward_line(double2 *g, double2 *wb, const doub
                 out.x = 2.0 * invN * (E.x + wO.x);
                 out.y = 2.0 * invN * (E.y + wO.y);
             }
-            if (!(dbg & 16)) gstore16(dst + 2 * k, out);
+            gstore16(dst + 2 * k, out);
         }
     }
     wave_sync();
 }
 
-// WAVES lines (wavefronts) per workgroup; DBG compiles the timing-ablation switches in (FftDev::dbg bits:
-// 1 no butterfly math, 4 no global loads, 16 no global stores, 32 no forward transforms)
-template <int C, int NT, int WAVES, bool DBG, int OCC, bool TWREG = false>
-__global__ void __launch_bounds__(64 * WAVES, OCC)
+// GW_WAVES lines (wavefronts) per workgroup, two workgroups per SIMD (8 waves per workgroup and 3 workgroups per SIMD were
+// measured in round 5 and rejected: profiles/r5_fused_variants.txt)
+constexpr int GW_WAVES = GRIDWAVE_WAVES;
+template <int C, int NT, bool TWREG>
+__global__ void __launch_bounds__(64 * GW_WAVES, 2)
 gridwave_bilinear_kernel(FftDev p, FusedArgs f, long nlines) {
-    constexpr int GW_T = 64 * WAVES, GW_WAVES = WAVES;
-    const int dbg = DBG ? p.dbg : 0;
+    constexpr int GW_T = 64 * GW_WAVES;
     using G = GW<C>;
     extern __shared__ double2 lds[];
     double2 *tw = lds;                                   // twiddle tables (GW<C>::T_*)
@@ -348,17 +340,14 @@ gridwave_bilinear_kernel(FftDev p, FusedArgs f, long nlines) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) t2r[i] = tw[G::T_2 + i * G::STR + lc];
     }
-    // a wave takes several lines (grid = lines / (waves x DDH_GW_LPW)): the table fill, the argument staging and the
+    // a wave takes several lines (grid = lines / (waves x FusedPlan::lpw)): the table fill, the argument staging and the
     // register twiddles are paid once per 8 lines instead of once per line (6.98 -> 6.85 ms at 768 x 384 lines of 768)
 #pragma unroll 1
   for (long line = (long)blockIdx.x * GW_WAVES + wave; line < nlines; line += (long)gridDim.x * GW_WAVES) {
     const long off = line * (long)M;
 
     LineLoads<NT> ld;
-    if (!(dbg & 4)) issue_loads<NT>(ld, s_src[0] + off, lane, K);
-    else
-#pragma unroll
-        for (int t = 0; t < NT; ++t) ld.x[t] = make_double2(1.0, 0.5);
+    issue_loads<NT>(ld, s_src[0] + off, lane, K);
     // One backward transform: operand l (already staged in ld) -> grid values g; prefetches operand l + 1.
     // Lane-derived addresses and constants are re-derived every time (a handful of integer operations)
     // instead of being hoisted out of the loops, where they would pin ~60 registers.
@@ -366,9 +355,9 @@ gridwave_bilinear_kernel(FftDev p, FusedArgs f, long nlines) {
         int ln = lane;
         asm volatile("" : "+v"(ln));
         double2 v[8];
-        build_z<C, NT>(ld, s_dscale[l], wb, tw, ln, v, dbg);
-        if (l + 1 < nloads && !(dbg & 4)) issue_loads<NT>(ld, s_src[l + 1] + off, ln, K);
-        backward_line<C, TWREG>(v, wb, tw, ln, g, dbg, t1r, t2r);
+        build_z<C, NT>(ld, s_dscale[l], wb, tw, ln, v);
+        if (l + 1 < nloads) issue_loads<NT>(ld, s_src[l + 1] + off, ln, K);
+        backward_line<C, TWREG>(v, wb, tw, ln, g, t1r, t2r);
     };
     // the `a` operands stay in registers (twice their grid values, like every transformed operand)
     double2 areg[FUSED_NA][C];
@@ -406,10 +395,10 @@ gridwave_bilinear_kernel(FftDev p, FusedArgs f, long nlines) {
             }
         }
         const int oc = s_flush[l];
-        if (oc >= 0 && !(dbg & 32)) {
+        if (oc >= 0) {
             int lf = lane;
             asm volatile("" : "+v"(lf));
-            forward_line<C, TWREG>(acc, wb, tw, lf, s_out[oc] + off, M, K, dbg, t1r);
+            forward_line<C, TWREG>(acc, wb, tw, lf, s_out[oc] + off, M, K, t1r);
 #pragma unroll
             for (int i = 0; i < C; ++i) acc[i] = make_double2(0.0, 0.0);
         }
@@ -417,69 +406,132 @@ gridwave_bilinear_kernel(FftDev p, FusedArgs f, long nlines) {
   }
 }
 
-template <int C, int WAVES, int OCC>
-int launch_cw(const FftDev &d, const FusedArgs &f_in, long nlines, hipStream_t st) {
-    using G = GW<C>;
+// executes a FusedPlan of this generation; f must have been built with one load per batch
+template <int C>
+static int launch_c(const FusedPlan &fp, const FftDev &d, const FusedArgs &f_in, long nlines, hipStream_t st) {
     constexpr int NT32 = (2 * C + 2) / 3;                  // 64-pair blocks that hold M/2 = N/3 pairs (3/2 dealiasing)
-    // lines per wave: 8 when that still leaves >= 2048 workgroups (8 per CU), fewer for small problems (2-D: a few
-    // hundred lines in all)
-    static const int lpw_env = getenv("DDH_GW_LPW") ? std::max(1, atoi(getenv("DDH_GW_LPW"))) : 0;
-    const long lpw = lpw_env ? lpw_env : std::min<long>(8, std::max<long>(1, nlines / ((long)WAVES * 2048)));
-    const long nwg = (nlines + (long)WAVES * lpw - 1) / ((long)WAVES * lpw);
-    if ((unsigned long)nwg > 0x7fffffffUL) return fail("rfft_bilinear_fused: grid too large");
-    const size_t lds = ((size_t)G::TW + (size_t)WAVES * G::LDW) * sizeof(double2);
-    const dim3 grid((unsigned)nwg), block(64 * WAVES);
-    const bool narrow = d.K + 1 <= 64 * NT32;
-    static const bool twreg = getenv("DDH_GW_TWREG") ? atoi(getenv("DDH_GW_TWREG")) != 0 : true;
+    const dim3 grid(fp.grid), block(fp.block);
     FusedArgs f = f_in;
     for (int t = 0; t < FUSED_TERMS; ++t) f.coef[t] *= 0.25;     // both factors of a term arrive doubled
-    if (C == 6 && d.dbg && narrow)                         // timing ablations (tools/bench_fused.py)
-        hipLaunchKernelGGL((gridwave_bilinear_kernel<C, NT32, WAVES, C == 6, OCC>), grid, block, lds, st, d, f, nlines);
-    else if (narrow && twreg && C == 6 && OCC == 2)
-        hipLaunchKernelGGL((gridwave_bilinear_kernel<C, NT32, WAVES, false, OCC, (C == 6 && OCC == 2)>), grid, block, lds, st, d, f,
-                           nlines);
-    else if (narrow)
-        hipLaunchKernelGGL((gridwave_bilinear_kernel<C, NT32, WAVES, false, OCC>), grid, block, lds, st, d, f, nlines);
+    if (fp.twreg)       // (C = 6 only)
+        hipLaunchKernelGGL((gridwave_bilinear_kernel<C, NT32, C == 6>), grid, block, fp.lds, st, d, f, nlines);
+    else if (fp.NT == NT32)
+        hipLaunchKernelGGL((gridwave_bilinear_kernel<C, NT32, false>), grid, block, fp.lds, st, d, f, nlines);
     else
-        hipLaunchKernelGGL((gridwave_bilinear_kernel<C, C, WAVES, false, OCC>), grid, block, lds, st, d, f, nlines);
+        hipLaunchKernelGGL((gridwave_bilinear_kernel<C, C, false>), grid, block, fp.lds, st, d, f, nlines);
     DDH_HIP(hipGetLastError());
     return 0;
 }
 
-template <int C>
-int launch_c(const FftDev &d, const FusedArgs &f, long nlines, hipStream_t st) {
-    static const int waves = getenv("DDH_GW_WAVES") ? atoi(getenv("DDH_GW_WAVES")) : 4;
-    static const int occ = getenv("DDH_GW_OCC") ? atoi(getenv("DDH_GW_OCC")) : 2;
-    if (C == 6 && occ == 3) return launch_cw<C, 4, (C == 6 ? 3 : 2)>(d, f, nlines, st);
-    if (waves == 8) return launch_cw<C, 8, 2>(d, f, nlines, st);
-    return launch_cw<C, 4, 2>(d, f, nlines, st);
-}
-
 }  // namespace gw
 
-using namespace gw;
+// The sizes the wave-per-line kernels are instantiated for: X(C), N = 128 C grid points
+#define DDH_GRIDWAVE_SIZES(X) X(2) X(3) X(4) X(6) X(8)
 
-bool gridwave_supported(const FftDev &d) {
-    static const bool off = getenv("DDH_FUSED_OLD") != nullptr;
-    if (off) return false;
-    if (d.N % 128 != 0 || (d.M & 1) || d.M < 2 || d.M > d.N) return false;
-    const int C = d.N / 128;
-    return C == 2 || C == 3 || C == 4 || C == 6 || C == 8;
+// a wave kernel of either generation exists for lines of N grid points / M coefficients; LDS bytes per workgroup of each
+static bool gridwave_supported(int N, int M, size_t &lds1, size_t &lds2) {
+    if (N % 128 != 0 || (M & 1) || M < 2 || M > N) return false;
+#define DDH_X(CV)                                                                                              \
+    if (N == 128 * CV) {                                                                                       \
+        lds1 = ((size_t)gw::GW<CV>::TW + (size_t)gw::GW_WAVES * gw::GW<CV>::LDW) * sizeof(double2);            \
+        lds2 = ((size_t)gw2::G2<CV>::TW + (size_t)gw::GW_WAVES * gw2::G2<CV>::LDW) * sizeof(double2);          \
+        return true;                                                                                           \
+    }
+    DDH_GRIDWAVE_SIZES(DDH_X)
+#undef DDH_X
+    return false;
 }
 
-bool gridwave2_supported(const FftDev &d);                                       // ddh_gridwave2.hip
-int launch_gridwave2(const FftDev &d, const FusedArgs &f, long nlines, hipStream_t st);
-
-// f must have been built with one load per batch
-int launch_gridwave(const FftDev &d, const FusedArgs &f, long nlines, hipStream_t st) {
-    if (!d.dbg && gridwave2_supported(d)) return launch_gridwave2(d, f, nlines, st);
-    switch (d.N / 128) {
-        case 2: return launch_c<2>(d, f, nlines, st);
-        case 3: return launch_c<3>(d, f, nlines, st);
-        case 4: return launch_c<4>(d, f, nlines, st);
-        case 6: return launch_c<6>(d, f, nlines, st);
-        case 8: return launch_c<8>(d, f, nlines, st);
+// Which kernel ddh_rfft_bilinear_fused takes, on which internal grid.
+FusedPlan fused_plan(const FftDev &d, long nlines) {
+    // A/B and fallback selectors (read here and nowhere else).  DDH_FUSED_OLD=1: the workgroup-per-line-pair kernel;
+    // DDH_FUSED_WIDER=0: the plan's own grid size only; DDH_GW_V2=0: first generation, 2: second generation also for
+    // truncated spectra (register loads); DDH_GW_DMA=0: register loads, 2: LDS-DMA without register twiddles
+    static const bool old = getenv("DDH_FUSED_OLD") != nullptr;
+    static const bool wider = !(getenv("DDH_FUSED_WIDER") && atoi(getenv("DDH_FUSED_WIDER")) == 0);
+    static const int v2 = getenv("DDH_GW_V2") ? atoi(getenv("DDH_GW_V2")) : 1;
+    static const int dma = getenv("DDH_GW_DMA") ? atoi(getenv("DDH_GW_DMA")) : 1;
+    FusedPlan fp{};
+    // A WIDER INTERNAL GRID where this grid size has no wave kernel (round 6).  The stage maps coefficient lines to
+    // coefficient lines; its grid never reaches memory.  Bilinear products of lines with modes <= K are free of aliasing in
+    // the retained modes on ANY grid of N' > 3 K points, so the stage may run on the smallest N' >= N the wave kernels are
+    // instantiated for (N' = 128 C) and returns the same coefficients up to round-off -- e.g. 192-point lines (128 modes) on
+    // 256 points, 576-point lines (384 modes) on 768 -- instead of the workgroup-per-line-pair kernel (0.05-0.12 of the HBM
+    // rate, profiles/r6_offsize_configs.txt).
+    // TODO (first item): an under-dealiased plan (N <= 3 K) is widened too, which removes the aliasing the
+    // caller's own grid would have produced.
+    const int sizes[] = {d.N, 256, 384, 512, 768, 1024};
+    size_t lds1 = 0, lds2 = 0;
+    bool wave = false;
+    fp.N = d.N;
+    for (int i = 0; i < 6 && !wave && !old; ++i) {
+        const int Np = sizes[i];
+        if (i > 0 && !(wider && Np >= d.N && Np > 3 * d.K)) continue;
+        if (gridwave_supported(Np, d.M, lds1, lds2)) {
+            fp.N = Np;
+            wave = true;
+        }
     }
+    const int N = fp.N, T = FUSED_T;
+    const int K = fourier_kmax(N, d.M);                    // of the internal grid's plan
+    if ((long)N > 6L * T) {
+        fp.error = "rfft_bilinear_fused: axis too long for the fused kernel";
+        return fp;
+    }
+    if (!wave) {
+        // one workgroup per line pair; operands transformed together: 3 when the points fit 3 per thread and 12 staged
+        // values per thread
+        fp.kernel = FusedKernel::workgroup;
+        fp.PTS = (long)N <= 3L * T ? 3 : 6;
+        fp.G = ((long)N <= 3L * T && 3L * N <= 12L * T) ? 3 : 1;
+        const long npairs = (nlines + 1) / 2;
+        if ((unsigned long)npairs > 0x7fffffffUL) {
+            fp.error = "rfft_bilinear_fused: grid too large";
+            return fp;
+        }
+        fp.grid = (unsigned)npairs;
+        fp.block = T;
+        fp.lds = ((size_t)d.ld * fp.G + (size_t)tw_entries(N)) * sizeof(double2);
+        return fp;
+    }
+    // one wavefront per line
+    fp.G = 1;
+    fp.C = N / 128;
+    const int NT32 = (2 * fp.C + 2) / 3;                   // 64-pair blocks that hold M/2 = N/3 pairs (3/2 dealiasing)
+    // Second generation: default for 3/2-padded lines whose stored pairs fill their 64-pair blocks exactly (K + 1 == 64 NT:
+    // 768 / 512, 384 / 256), with LDS-DMA staging and register twiddles (the measurements: ddh_gridwave2.hip)
+    const bool exact = K + 1 == 64 * NT32;
+    if (v2 != 0 && (fp.C == 3 || fp.C == 6) && (exact || (v2 == 2 && K + 1 <= 64 * NT32))) {
+        fp.kernel = FusedKernel::gridwave2;
+        fp.NT = NT32;
+        fp.dma = dma != 0 && exact;
+        fp.twreg = fp.dma && dma == 1;     // (register loads leave no room for register twiddles: 256 VGPRs + scratch)
+        fp.lds = lds2;
+    } else {
+        fp.kernel = FusedKernel::gridwave;
+        const bool narrow = K + 1 <= 64 * NT32;
+        fp.NT = narrow ? NT32 : fp.C;
+        fp.twreg = narrow && fp.C == 6;    // the lane's 15 radix-8 twiddles in registers: the size with room for them
+        fp.lds = lds1;
+    }
+    // lines per wave: 8 when that still leaves >= 2048 workgroups (8 per CU), fewer for small problems (2-D: a few
+    // hundred lines in all)
+    fp.lpw = std::min<long>(8, std::max<long>(1, nlines / ((long)gw::GW_WAVES * 2048)));
+    const long nwg = (nlines + gw::GW_WAVES * fp.lpw - 1) / (gw::GW_WAVES * fp.lpw);
+    if ((unsigned long)nwg > 0x7fffffffUL) {
+        fp.error = "rfft_bilinear_fused: grid too large";
+        return fp;
+    }
+    fp.grid = (unsigned)nwg;
+    fp.block = 64 * gw::GW_WAVES;
+    return fp;
+}
+
+int launch_gridwave(const FusedPlan &fp, const FftDev &d, const FusedArgs &f, long nlines, hipStream_t st) {
+#define DDH_X(CV) \
+    if (fp.C == CV) return gw::launch_c<CV>(fp, d, f, nlines, st);
+    DDH_GRIDWAVE_SIZES(DDH_X)
+#undef DDH_X
     return fail("gridwave: unsupported size");
 }
 

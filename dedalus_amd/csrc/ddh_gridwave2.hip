@@ -247,59 +247,35 @@ gridwave2_bilinear_kernel(FftDev p, FusedArgs f, long nlines) {
   }
 }
 
+// executes a FusedPlan of this generation (fused_plan, ddh_gridwave.hip); f must have been built with one load per batch
 template <int C>
-int launch_c(const FftDev &d, const FusedArgs &f_in, long nlines, hipStream_t st) {
-    using G = G2<C>;
-    constexpr int WAVES = 4;
+static int launch_c(const FusedPlan &fp, const FftDev &d, const FusedArgs &f_in, long nlines, hipStream_t st) {
+    constexpr int WAVES = GRIDWAVE_WAVES;
     constexpr int NT32 = (2 * C + 2) / 3;                  // 64-pair blocks that hold M/2 = N/3 pairs (3/2 dealiasing)
-    static const int lpw_env = getenv("DDH_GW_LPW") ? std::max(1, atoi(getenv("DDH_GW_LPW"))) : 0;
-    const long lpw = lpw_env ? lpw_env : std::min<long>(8, std::max<long>(1, nlines / ((long)WAVES * 2048)));
-    const long nwg = (nlines + (long)WAVES * lpw - 1) / ((long)WAVES * lpw);
-    if ((unsigned long)nwg > 0x7fffffffUL) return fail("rfft_bilinear_fused: grid too large");
-    const size_t lds = ((size_t)G::TW + (size_t)WAVES * G::LDW) * sizeof(double2);
-    const dim3 grid((unsigned)nwg), block(64 * WAVES);
-    static const bool twreg = getenv("DDH_GW_TWREG") ? atoi(getenv("DDH_GW_TWREG")) != 0 : false;   // (spills: see below)
-    static const int dma = getenv("DDH_GW_DMA") ? atoi(getenv("DDH_GW_DMA")) : 1;     // 1: LDS-DMA staging + register twiddles, 2: without, 0: register loads
+    const dim3 grid(fp.grid), block(fp.block);
     FusedArgs f = f_in;
     for (int t = 0; t < FUSED_TERMS; ++t) f.coef[t] *= 0.25;     // both factors of a term arrive doubled
-    if (dma && d.K + 1 == 64 * NT32) {
-        if (dma == 1)
-            hipLaunchKernelGGL((gridwave2_bilinear_kernel<C, NT32, WAVES, true, true>), grid, block, lds, st, d, f, nlines);
-        else
-            hipLaunchKernelGGL((gridwave2_bilinear_kernel<C, NT32, WAVES, false, true>), grid, block, lds, st, d, f, nlines);
-    } else if (twreg)
-        hipLaunchKernelGGL((gridwave2_bilinear_kernel<C, NT32, WAVES, true>), grid, block, lds, st, d, f, nlines);
+    if (fp.dma && fp.twreg)
+        hipLaunchKernelGGL((gridwave2_bilinear_kernel<C, NT32, WAVES, true, true>), grid, block, fp.lds, st, d, f, nlines);
+    else if (fp.dma)
+        hipLaunchKernelGGL((gridwave2_bilinear_kernel<C, NT32, WAVES, false, true>), grid, block, fp.lds, st, d, f, nlines);
     else
-        hipLaunchKernelGGL((gridwave2_bilinear_kernel<C, NT32, WAVES, false>), grid, block, lds, st, d, f, nlines);
+        hipLaunchKernelGGL((gridwave2_bilinear_kernel<C, NT32, WAVES, false>), grid, block, fp.lds, st, d, f, nlines);
     DDH_HIP(hipGetLastError());
     return 0;
 }
 
 }  // namespace gw2
 
-// Default for 3/2-padded lines whose stored pairs fill their 64-pair blocks exactly (K + 1 == 64 NT: 768 / 512, 384 / 256):
-// the LDS-DMA variant with register twiddles.  Measured on MI355X at 768 x 384 lines of 768 points (tools/bench_fused.py,
-// same box, round 5): first generation 6.71 ms; this kernel with register loads 6.83 ms (no room for register twiddles:
-// with them 256 VGPRs + 44 B of scratch, 8.19 ms); LDS-DMA staging, one operand ahead 6.71 ms; two operands ahead 6.42 ms
-// (235 VGPRs), without register twiddles 6.59 ms.  Counters (profiles/r5_fused_sq_counters.txt): 6405 instead of 6897 VALU
-// and 1021 instead of 1135 LDS instructions per line, LDS bank-conflict cycles -64 %, s_waitcnt time -15 %.
-// DDH_GW_V2=0 keeps the first generation; other sizes take it anyway.
-bool gridwave2_supported(const FftDev &d) {
-    static const bool off = getenv("DDH_GW_V2") != nullptr && atoi(getenv("DDH_GW_V2")) == 0;
-    if (off) return false;
-    if (d.N % 128 != 0 || (d.M & 1) || d.M < 2 || d.M > d.N) return false;
-    const int C = d.N / 128;
-    if (!(C == 3 || C == 6)) return false;
-    const int NT32 = (2 * C + 2) / 3;
-    static const bool any_k = getenv("DDH_GW_V2") != nullptr && atoi(getenv("DDH_GW_V2")) == 2;   // 2: also truncated spectra (register loads)
-    if (any_k) return d.K + 1 <= 64 * NT32 && NT32 < C;
-    return d.K + 1 == 64 * NT32 && NT32 < C;
-}
-
-int launch_gridwave2(const FftDev &d, const FusedArgs &f, long nlines, hipStream_t st) {
-    switch (d.N / 128) {
-        case 3: return gw2::launch_c<3>(d, f, nlines, st);
-        case 6: return gw2::launch_c<6>(d, f, nlines, st);
+// Measured on MI355X at 768 x 384 lines of 768 points (tools/bench_fused.py, same box, round 5): first generation 6.71 ms;
+// this kernel with register loads 6.83 ms (no room for register twiddles: with them 256 VGPRs + 44 B of scratch, 8.19 ms);
+// LDS-DMA staging, one operand ahead 6.71 ms; two operands ahead 6.42 ms (235 VGPRs), without register twiddles 6.59 ms.
+// Counters (profiles/r5_fused_sq_counters.txt): 6405 instead of 6897 VALU and 1021 instead of 1135 LDS instructions per
+// line, LDS bank-conflict cycles -64 %, s_waitcnt time -15 %.
+int launch_gridwave2(const FusedPlan &fp, const FftDev &d, const FusedArgs &f, long nlines, hipStream_t st) {
+    switch (fp.C) {
+        case 3: return gw2::launch_c<3>(fp, d, f, nlines, st);
+        case 6: return gw2::launch_c<6>(fp, d, f, nlines, st);
     }
     return fail("gridwave2: unsupported size");
 }

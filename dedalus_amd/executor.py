@@ -207,26 +207,32 @@ class HipExecutor:
             libhip.call("ddh_fft_set_stage_window", h, int(z0), int(cw))
             wcur[h.value] = (int(z0), int(cw))
 
-    # (grid, coefficient) sizes the wave-per-four-line-pairs kernels are instantiated for (csrc/ddh_fftwave.hip:
-    # DDH_CHEB_WAVE_SIZES, launch_wave_rfft_kind)
-    WAVE_CHEB_SIZES = frozenset([(384, 256), (192, 128), (256, 256), (192, 192), (128, 128), (64, 64), (256, 128), (128, 64)])
-    WAVE_RFFT_SIZES = frozenset([(768, 512), (576, 384), (384, 256), (192, 128)])
+    @staticmethod
+    def _wave_size(spec):
+        """Does the library have a wave-per-four-line-pairs kernel for this transform's (grid, coefficient) size?  The
+        library's own table (ddh_fft_wave_size: no plan, no device)."""
+        kind = {"rfft": 0, "cheb": 1}.get(spec[0])
+        if kind is None:
+            return False
+        covered = C.c_int(0)
+        libhip.call("ddh_fft_wave_size", kind, int(spec[1]), int(spec[2]), C.byref(covered))
+        return bool(covered.value)
 
     def stage_layout_ok(self, zspec, xspec, nx, ny):
         """Can the array between the z and the x transforms be x-blocked?  (both run as strided wave kernels)"""
-        return (zspec[0] == "cheb" and (int(zspec[1]), int(zspec[2])) in self.WAVE_CHEB_SIZES and xspec[0] == "rfft"
-                and (int(xspec[1]), int(xspec[2])) in self.WAVE_RFFT_SIZES and nx % 64 == 0 and ny % 8 == 0
+        return (zspec[0] == "cheb" and self._wave_size(zspec) and xspec[0] == "rfft"
+                and self._wave_size(xspec) and nx % 64 == 0 and ny % 8 == 0
                 and int(xspec[2]) == nx)
 
     def stage_block_ok(self, xspec, nx, nx_local, ny):
         """Sharded run: can the x transforms read / write the exchanged layout [p][z][nx / P][ky] in place?  (real-Fourier
         wave kernels, blocks of 64 / 128 / 256 rows)"""
-        return (xspec[0] == "rfft" and (int(xspec[1]), int(xspec[2])) in self.WAVE_RFFT_SIZES and int(xspec[2]) == nx
+        return (xspec[0] == "rfft" and self._wave_size(xspec) and int(xspec[2]) == nx
                 and nx_local in (64, 128, 256) and nx % nx_local == 0 and ny % 2 == 0)
 
     def tiled_forward_ok(self, spec, basis, inner, row_len):
         """Can `transform(..., "forward", tiled_row=row_len)` run?  (the strided-axis wave kernel's sizes)"""
-        return (spec[0] == "cheb" and (int(spec[1]), int(spec[2])) in self.WAVE_CHEB_SIZES and inner > 1
+        return (spec[0] == "cheb" and self._wave_size(spec) and inner > 1
                 and row_len % 8 == 0 and inner % row_len == 0 and (inner // row_len) % 8 == 0)
 
     def _transform(self, spec, basis, direction, src, dst, outer, inner, deriv=0.0, tiled_row=0, xb=0):

@@ -132,6 +132,11 @@ int ddh_fft_set_stage_block(ddh_handle plan, int rows);
  * take.  The reference's plans are size-generic (core/transforms.py:537-565, 801-902); here the kernel is chosen per
  * (grid, coefficient) size, and tests assert which one a size took.                                                   */
 int ddh_fft_wave_launches(long *count);
+/* ... and which sizes those tables hold, without a plan or a device: *covered = 1 when lines of n_grid points / n_coeff
+ * coefficients have a wave kernel, kind 0 = real Fourier (strided axis), 1 = Chebyshev (either axis).  Callers that choose
+ * array layouts only the wave kernels read (ddh_fft_set_stage_layout, ddh_cheb_forward_tiled) ask this instead of keeping
+ * a copy of the tables.                                                                                               */
+int ddh_fft_wave_size(int kind, int n_grid, int n_coeff, int *covered);
 int ddh_cheb_backward(ddh_handle plan, const double *c, double *g, long outer, long inner, void *stream);
 
 /* Dense matrix-multiply transform along an axis (JacobiMMT core/transforms.py:114-158 via

@@ -37,7 +37,8 @@ def _plan(N, M, alpha):
     return h, conv
 
 
-# every (grid, coefficient) size the wave Chebyshev kernels are instantiated for (csrc/ddh_fftwave.hip: DDH_CHEB_WAVE_SIZES)
+# every (grid, coefficient) size the wave Chebyshev kernels are instantiated for (csrc/ddh_fft_dev.h: DDH_CHEB_WAVE_SIZES,
+# DDH_RFFT_WAVE_SIZES)
 WAVE_CHEB_SIZES = [(384, 256), (192, 128), (256, 256), (192, 192), (128, 128), (64, 64), (256, 128), (128, 64)]
 WAVE_RFFT_SIZES = [(768, 512), (576, 384), (384, 256), (192, 128)]
 

@@ -53,3 +53,18 @@ def test_fused_grid_stage_does_not_spill():
     k = [n for n in u if "gridwave2_bilinear_kernelILi6ELi4ELi4ELb1ELb1E" in n]
     assert len(k) == 1, list(u)
     assert u[k[0]]["scratch"] == 0 and u[k[0]]["vgprs"] <= 256 and u[k[0]]["waves"] >= 2, u[k[0]]
+
+
+def test_workgroup_grid_stage_does_not_gain_scratch():
+    """fused_rfft_bilinear_kernel<PTS, G> (the fused grid stage where no wave kernel covers the line length) sits at the
+    256-VGPR limit of two workgroups per CU, and its allocation has moved by hundreds of bytes of scratch with one-line
+    edits (csrc/ddh_fft.hip, the bound on the swizzled workgroup index).  The bounds are what the kernel had with its
+    timing switches still compiled in -- <3,1>: 227 VGPRs / 0 B, <3,3>: 239 / 0 B, <6,1>: 256 / 80 B -- which their removal
+    may not exceed; today <3,1>: 213 / 0, <3,3>: 225 / 0, <6,1>: 256 / 24.  A compiler that spills here shows up in this test."""
+    u = _usage("ddh_fft.hip")
+    bound = {"ILi3ELi1EE": 0, "ILi3ELi3EE": 0, "ILi6ELi1EE": 80}
+    for inst, scratch in bound.items():
+        k = [n for n in u if "fused_rfft_bilinear_kernel" + inst in n]
+        assert len(k) == 1, list(u)
+        print(k[0], u[k[0]])
+        assert u[k[0]]["scratch"] <= scratch and u[k[0]]["vgprs"] <= 256 and u[k[0]]["waves"] >= 2, (k[0], u[k[0]])

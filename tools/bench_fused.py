@@ -1,6 +1,7 @@
 """Timing of the fused grid stage alone at the 3-D Rayleigh-Benard line sizes (u.grad(b), u.grad(u):
-3 + 12 operands, 4 results), for kernel experiments.  Environment knobs are read by the library:
-DDH_FFT_DBG (ablations), DDH_GW_WAVES (waves per workgroup), DDH_FUSED_OLD=1 (workgroup-per-pair kernel)."""
+3 + 12 operands, 4 results), for kernel experiments.  Environment knobs are read by the library (fused_plan):
+DDH_FUSED_OLD=1 (workgroup-per-pair kernel), DDH_GW_V2=0 (first-generation wave kernel), DDH_GW_DMA=0 / 2 (second
+generation with register loads / without register twiddles)."""
 import os
 import sys
 
@@ -55,10 +56,9 @@ def main():
     nbytes = 19 * nl * Ny * 8
     chk = [float(oo[i].abs().sum().item()) for i in range(4)]
     print("data=%s " % data, end="")
-    print("fused grid stage %d lines  dbg=%s waves=%s old=%s v1=%s twreg=%s lpw=%s: %.3f ms  %.0f GB/s  checksums %s" % (
-        nl, os.environ.get("DDH_FFT_DBG", "0"), os.environ.get("DDH_GW_WAVES", "4"),
-        os.environ.get("DDH_FUSED_OLD", "0"), os.environ.get("DDH_GW_V1", "0"), os.environ.get("DDH_GW_TWREG", "1"),
-        os.environ.get("DDH_GW_LPW", "-"), ms, nbytes / ms / 1e6, " ".join("%.15e" % c for c in chk)), flush=True)
+    print("fused grid stage %d lines  old=%s v2=%s dma=%s: %.3f ms  %.0f GB/s  checksums %s" % (
+        nl, os.environ.get("DDH_FUSED_OLD", "0"), os.environ.get("DDH_GW_V2", "1"), os.environ.get("DDH_GW_DMA", "1"),
+        ms, nbytes / ms / 1e6, " ".join("%.15e" % c for c in chk)), flush=True)
 
 
 if __name__ == "__main__":

@@ -52,18 +52,6 @@ def main():
         bytes_ = (c.numel() + g.numel()) * 8
         tb = timeit(dev, lambda: libhip.call("ddh_%s_backward" % kind, p, ptr(c), ptr(g), cs[0], cs[2], dev.stream))
         tf = timeit(dev, lambda: libhip.call("ddh_%s_forward" % kind, p, ptr(g), ptr(c2), cs[0], cs[2], dev.stream))
-        if os.environ.get("DDH_FFT_PROF"):
-            lib = libhip.load()
-            lib.ddh_debug_fft_prof.argtypes = [C.c_uint64, C.POINTER(C.c_double)]
-            out = (C.c_double * 4)()
-            # counters accumulated over both directions' launches: reset, then one bwd and one fwd
-            lib.ddh_debug_fft_prof(p, out)
-            libhip.call("ddh_%s_backward" % kind, p, ptr(c), ptr(g), cs[0], cs[2], dev.stream); dev.sync()
-            lib.ddh_debug_fft_prof(p, out); b4 = list(out)
-            libhip.call("ddh_%s_forward" % kind, p, ptr(g), ptr(c2), cs[0], cs[2], dev.stream); dev.sync()
-            lib.ddh_debug_fft_prof(p, out); f4 = list(out)
-            print("   phase cycles/WG  bwd: load %.0f fft %.0f store %.0f | fwd: load %.0f fft %.0f store %.0f  (WGs %d)"
-                  % (b4[0], b4[1], b4[2], f4[0], f4[1], f4[2], int(b4[3])))
         print("%s  bwd %.3f ms %.0f GB/s | fwd %.3f ms %.0f GB/s   (%.2f GB/pass)" %
               (name, tb * 1e3, bytes_ / tb / 1e9, tf * 1e3, bytes_ / tf / 1e9, bytes_ / 1e9), flush=True)
         del c, g, c2
@@ -78,21 +66,6 @@ def main():
     terms = [(0, j, j, 1.0) for j in range(3)] + [(1 + c, j, 3 + 3 * j + c, 1.0) for c in range(3) for j in range(3)]
     tfz = timeit(dev, lambda: hx.rfft_bilinear_fused(("rfft", Gy, Ny), None, [a[i] for i in range(3)],
                                                      [bb[i] for i in range(12)], [oo[i] for i in range(4)], nl, terms))
-    if os.environ.get("DDH_FFT_PROF"):
-        lib = libhip.load()
-        lib.ddh_debug_fft_prof.argtypes = [C.c_uint64, C.POINTER(C.c_double)]
-        out = (C.c_double * 4)()
-        ph = hx._plan(("rfft", Gy, Ny), None)[1]
-        lib.ddh_debug_fft_prof(ph, out)
-        hx.rfft_bilinear_fused(("rfft", Gy, Ny), None, [a[i] for i in range(3)], [bb[i] for i in range(12)],
-                               [oo[i] for i in range(4)], nl, terms)
-        dev.sync()
-        lib.ddh_debug_fft_prof(ph, out)
-        vals = [out[0] * out[3], out[1] * out[3], out[2] * out[3], out[3]]    # the hook divides by slot 3
-        tot = sum(vals)
-        nwg = (nl + 1) // 2
-        print("   fused phase clocks per WG: wait %.0f unpack %.0f fft %.0f rest %.0f  -> %% %s"
-              % tuple([v / nwg for v in vals] + [[round(100 * x / tot, 1) for x in vals]]))
     nbytes = 19 * nl * Ny * 8
     print("y  fused grid stage (19 lines arrays, %d lines): %.3f ms %.0f GB/s -> full size %.2f ms"
           % (nl, tfz * 1e3, nbytes / tfz / 1e9, tfz * 1e3 * Gz * Gx / nl), flush=True)

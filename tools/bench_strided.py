@@ -1,7 +1,7 @@
 """Micro-benchmark of the strided-axis transforms at the 3-D Rayleigh-Benard shapes (512 x 512 x 256, dealias 3/2),
 one launch as the solver issues it: z Chebyshev dual backward (field + d/dz), z forward into the (3/2, 3/2) basis,
 x real-FFT backward (single, dual) and forward.  Prints ms and algorithmic GB/s (bytes read + written once).
-Environment switches of the library (DDH_FFT_WAVE, DDH_FFT_TPW, ...) are read once per process: run one process
+The environment switch of the library (DDH_FFT_WAVE, the mask of transform_plan) is read once per process: run one process
 per variant.  NCOMP components per launch (default 3)."""
 import ctypes as C
 import os
