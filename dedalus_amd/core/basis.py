@@ -105,6 +105,32 @@ class RealFourier(Basis):
             return self
         return NotImplemented
 
+    # ---- reduction vectors along this axis (act on coefficient vectors) -------------------------------
+    def interpolate_vector(self, position):
+        """InterpolateRealFourier (basis.py:1227-1249): interleaved cos(m x), -sin(m x) at the native coordinate
+        x = 2 pi (position - left) / L.  The -sin slot of m = 0 multiplies an invalid mode (basis.py:1123-1134)."""
+        position = resolve_position(self, position)
+        xn = 2 * np.pi * (position - self.bounds[0]) / self.length
+        m = np.arange(self.size // 2)
+        v = np.zeros(self.size)
+        v[0::2] = np.cos(m * xn)
+        v[1::2] = -np.sin(m * xn)
+        return v
+
+    def integrate_vector(self):
+        """IntegrateRealFourier (basis.py:1252-1275): integ cos(m x) = L delta(m, 0), integ -sin(m x) = 0."""
+        v = np.zeros(self.size)
+        v[0] = self.length
+        return v
+
+
+def resolve_position(basis, position):
+    """'left' / 'right' / 'center' -> coordinate (operators.py Interpolate._preprocess_args role)."""
+    if isinstance(position, str):
+        lo, hi = basis.bounds
+        return {"left": lo, "right": hi, "center": 0.5 * (lo + hi)}[position]
+    return float(position)
+
 
 class Jacobi(Basis):
     """Jacobi polynomial basis on the (a0, b0) Gauss grid (basis.py:432-640)."""

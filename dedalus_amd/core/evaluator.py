@@ -20,6 +20,7 @@ import os
 import numpy as np
 
 from . import operators as ops
+from . import reduced
 from .field import Field
 from .polyop import flatten
 from .problems import LinCtx
@@ -131,6 +132,8 @@ class Evaluator:
         self._lin_cache = {}
         self._const_cache = {}
         self._canon = {}
+        self._hoisted = {}              # id(expr) -> (expr, reductions, inner) of reduced.hoist
+        self._red_weights = {}          # device weight vectors of the reductions
         self.cache = {}
 
     # ---- geometry ------------------------------------------------------------------------------------
@@ -316,13 +319,53 @@ class Evaluator:
             res = self.ex.empty((expr.ncomp,) + tuple(expr.domain.storage_coeff_shape()))
             self.dist.transformer.forward_data(expr.domain, expr.ncomp, g, expr.domain.dealias, res)
         else:
-            le = self._lin(expr)
             if not _full_sep(self.dist, expr.domain):
-                raise NotImplementedError("evaluating expressions without all Fourier bases")
-            res = self.apply_linear(le, expr.domain)
+                res = self._eval_reduced(expr)
+            else:
+                res = self.apply_linear(self._lin(expr), expr.domain)
             res = res.reshape((expr.ncomp,) + tuple(expr.domain.storage_coeff_shape()))
         self.cache[key] = res
         return res
+
+    # ---- reduced domains (core/reduced.py) --------------------------------------------------------------------------
+    def _eval_reduced(self, expr):
+        """Coefficient data of a linear expression whose domain lacks a Fourier basis: its reductions along Fourier axes
+        hoisted to the top (reduced.hoist), the rest evaluated on the full domain by the existing paths, then one
+        ddh_axis_contract per reduction -- mode-0 gathers first, they shrink what the interpolations read."""
+        reduced.check_single_rank(expr)
+        hit = self._hoisted.get(id(expr))
+        if hit is None:
+            hit = self._hoisted[id(expr)] = (expr,) + reduced.hoist(expr)
+        _, reds, inner = hit
+        if not reds:
+            return self._eval_reduced_generic(expr)
+        c = self.eval_coeff(inner)
+        shape = [inner.ncomp] + list(inner.domain.storage_coeff_shape())
+        c = c.reshape(shape)
+        dom = inner.domain
+        for red in sorted(reds, key=lambda r: r[0] == "interp"):
+            pos = 1 + self.dist.storage_order.index(red[1])
+            n, w = reduced.reduction_weights(dom, red)
+            wkey = (n, w.tobytes())
+            if wkey not in self._red_weights:
+                self._red_weights[wkey] = self.ex.from_host(w)
+            outer, inner_len = int(np.prod(shape[:pos])), int(np.prod(shape[pos + 1:]))
+            c = self.ex.axis_contract(c, outer, n, inner_len, self._red_weights[wkey], ostride=shape[pos] * inner_len)
+            shape[pos] = 1
+            dom = dom.replace(red[1], None)
+        return c
+
+    def _eval_reduced_generic(self, expr):
+        """A linear expression on a reduced domain whose reductions do not hoist (a sum of different slices, the gradient of
+        a profile): the Fourier reductions are leaves of its term list (Interpolate.lin outside the LHS context; their
+        data expanded to the k = 0 modes, _expand), the mat-vec pins the removed axes to k = 0, and that slab is the result."""
+        nf, nx, ny, kx, ky = self.geom()
+        res = self.apply_linear(self._lin(expr), expr.domain)
+        fx, fy = self._force_flags(expr.domain)
+        sx, sy = (1 if fx else nx), (1 if fy else ny)
+        out = self.ex.empty((res.shape[0], sx, sy))
+        self.ex.assign(out, res[:, :sx, :sy])
+        return out
 
     def eval_grid(self, expr):
         """Grid data at the dealias scales."""
@@ -845,6 +888,7 @@ class Evaluator:
 def evaluate_expression(expr):
     """expr.evaluate(): returns a new Field holding the value (operators.py Future.evaluate)."""
     dist = expr.dist
+    reduced.check_single_rank(expr)
     ev = getattr(dist, "_default_evaluator", None)
     if ev is None:
         ev = dist._default_evaluator = Evaluator(dist)

@@ -169,6 +169,9 @@ class Interpolate(LinearOperator):
         if b is None:
             return le
         if b.separable:
+            if ctx is not None and not getattr(ctx, "strict", True):
+                # run-time evaluation: a reduction of its own (core/reduced.py), a leaf of the expression above it
+                return LinExpr.identity(self, self.ncomp, self.dist.coupled_size(self.domain))
             raise NotImplementedError("interpolation along a Fourier axis couples all modes: unsupported")
         pos = self.position
         if isinstance(pos, str):
@@ -185,9 +188,17 @@ class Integrate(LinearOperator):
             if not isinstance(coords, (tuple, list)):
                 coords = (coords,)
             axes = []
-            for c in coords:
-                for cc in getattr(c, "coords", (c,)):
-                    axes.append(self.dist.coord_axis(cc))
+
+            def walk(c):
+                if isinstance(c, (tuple, list)):            # ave(b, ('x', 'y')): lists of coordinates, nested or not
+                    for cc in c:
+                        walk(cc)
+                elif isinstance(c, str):                    # names resolve to coordinates (operators.py:1177-1179)
+                    axes.append(self.dist.coord_axis(self.dist.get_coord(c)))
+                else:
+                    for cc in getattr(c, "coords", (c,)):
+                        axes.append(self.dist.coord_axis(cc))
+            walk(coords)
         self.axes = axes
         self.args = (operand, coords)
         dom = operand.domain

@@ -68,6 +68,9 @@ class Handler:
             name = str(task)
         expr = self.solver.problem._parse(task) if isinstance(task, str) else task
         layout = 'c' if layout in ('c', 'coeff') else 'g'
+        if hasattr(expr, "domain"):
+            from . import reduced
+            reduced.check_single_rank(expr, name)           # (Cartesian reductions of a sharded axis: refused up front)
         self.tasks.append(dict(operator=expr, layout=layout, name=name, scales=scales, out=None))
 
     def add_tasks(self, tasks, **kw):

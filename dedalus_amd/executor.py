@@ -345,6 +345,19 @@ class HipExecutor:
         mn, mx, sm = self._red_out.cpu().tolist()
         return mn, mx, sm
 
+    def axis_contract(self, x, outer, n, inner, w, ostride=None):
+        """out[o][j][i] = sum_k w[j][k] x[o][k][i] for x = [outer][n][inner] device data whose `outer` blocks lie ostride
+        doubles apart (default n * inner), w = [nw][n] device weights -> [outer][nw][inner] (ddh_axis_contract).  With
+        n = 1 and ostride = N * inner it gathers the k = 0 slab of an [outer][N][inner] array and reads nothing else."""
+        nw = int(w.shape[0])
+        ostride = int(n) * int(inner) if ostride is None else int(ostride)
+        x = x if x.is_contiguous() else x.contiguous()
+        out = self.empty((int(outer), nw, int(inner)))
+        libhip.note_cost("ddh_axis_contract", 2.0 * outer * nw * n * inner, 8.0 * outer * inner * (n + nw))
+        libhip.call("ddh_axis_contract", ptr(x), ptr(out), int(outer), int(n), int(inner), ostride, ptr(w), nw,
+                    self.dev.stream)
+        return out
+
     def a2a_plan(self, pcomm, n0, n1, n2, n3):
         """Library-owned transpose plan (ddh_a2a_plan on the RCCL communicator of `pcomm`), cached per shape; None when
         the exchange goes through torch.distributed (parallel.Comm.library_comm)."""

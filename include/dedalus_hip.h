@@ -333,6 +333,16 @@ int ddh_grid_cfl_spherical(double *result_d, const double *u, long n_ang, int nr
 #define DDH_REDUCE_WORK_DOUBLES 3072
 int ddh_grid_reduce(double *out3_d, const double *x, long n, double *work_d, void *stream);
 
+/* Contraction of one storage axis with nw (1..4) weight vectors, the device half of reduced analysis tasks:
+ *   in [outer][n][inner] with the blocks of one `outer` index ostride (>= n * inner) doubles apart, w [nw][n]
+ *   out[o][j][i] = sum_k w[j][k] * in[o][k][i],   out [outer][nw][inner] contiguous.
+ * Interpolation along a RealFourier axis (InterpolateRealFourier, core/basis.py:1227-1249: w = interleaved cos / -sin
+ * at the position) and, with n = 1 and ostride = N * inner, the mode-0 gather of IntegrateRealFourier /
+ * AverageRealFourier (core/basis.py:1252-1300), which reads the k = 0 slab only.  Fixed summation order (a function of
+ * n alone), no atomics: repeated calls are bit-identical; NaN-propagating.                                          */
+int ddh_axis_contract(const double *in_d, double *out_d, long outer, int n, long inner, long ostride,
+                      const double *w_d, int nw, void *stream);
+
 /* ---- pencil systems ------------------------------------------ */
 /* A "pencil pack" describes all pencils of a problem at once.  System vectors are real arrays
  * [nrows][nx][ny] (cell index fastest).  With nfourier real-Fourier separable axes a cell holds
