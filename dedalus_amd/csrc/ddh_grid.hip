@@ -97,8 +97,13 @@ struct CflArgs {
     int ncomp;
 };
 
+// NaN-propagating min / max (np.min / np.max semantics: a blown-up field must show up in flow.max(), fmin / fmax drop it)
+__device__ __forceinline__ double nan_min(double x, double y) { return (x != x) ? x : ((y != y) ? y : fmin(x, y)); }
+__device__ __forceinline__ double nan_max(double x, double y) { return (x != x) ? x : ((y != y) ? y : fmax(x, y)); }
+
 __device__ __forceinline__ void atomic_max_double(double *addr, double v) {
-    // values are non-negative: integer ordering == floating ordering
+    // values are non-negative or NaN: integer ordering == floating ordering, and a NaN's bit pattern (either sign) lies
+    // above +inf as an unsigned integer, so that a NaN from any block wins -- f.max() of the reference returns NaN too
     atomicMax(reinterpret_cast<unsigned long long *>(addr), (unsigned long long)__double_as_longlong(v));
 }
 
@@ -116,12 +121,12 @@ __global__ void __launch_bounds__(256) cfl_kernel(double *result, const double *
         }
         double f = 0.0;
         for (int c = 0; c < a.ncomp; ++c) f += fabs(u[(long)c * n + i]) * a.inv[c][idx[a.comp_axis[c]]];
-        m = fmax(m, f);
+        m = nan_max(m, f);
     }
     red[threadIdx.x] = m;
     __syncthreads();
     for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + s]);
+        if (threadIdx.x < s) red[threadIdx.x] = nan_max(red[threadIdx.x], red[threadIdx.x + s]);
         __syncthreads();
     }
     if (threadIdx.x == 0) atomic_max_double(result, red[0]);
@@ -139,12 +144,12 @@ cfl_spherical_kernel(double *result, const double *__restrict__ u, long n_ang, i
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const int ir = (int)(i % nr);
         const double up = u[i], ut = u[n + i], ur = u[2 * n + i];
-        m = fmax(m, sqrt(up * up + ut * ut) * inv_h[ir] + fabs(ur) * inv_dr[ir]);
+        m = nan_max(m, sqrt(up * up + ut * ut) * inv_h[ir] + fabs(ur) * inv_dr[ir]);
     }
     red[threadIdx.x] = m;
     __syncthreads();
     for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + s]);
+        if (threadIdx.x < s) red[threadIdx.x] = nan_max(red[threadIdx.x], red[threadIdx.x + s]);
         __syncthreads();
     }
     if (threadIdx.x == 0) atomic_max_double(result, red[0]);
@@ -242,10 +247,6 @@ a2av_unpack_kernel(const double *__restrict__ src, double *__restrict__ dst, lon
 // min / max / sum of n doubles: fixed-shape tree (block partials in a fixed order, then one block over the partials),
 // so the result does not depend on scheduling.  out3 = {min, max, sum}.
 constexpr int RED_BLOCKS = 1024;
-
-// NaN-propagating min / max (np.min / np.max semantics: a blown-up field must show up in flow.max(), fmin / fmax drop it)
-__device__ __forceinline__ double nan_min(double x, double y) { return (x != x) ? x : ((y != y) ? y : fmin(x, y)); }
-__device__ __forceinline__ double nan_max(double x, double y) { return (x != x) ? x : ((y != y) ? y : fmax(x, y)); }
 
 __device__ __forceinline__ void red3_combine(double &mn, double &mx, double &sm, double a, double b, double c) {
     mn = nan_min(mn, a);

@@ -9,6 +9,12 @@ compute_timestep() one step later (flow_tools.py:183-207)."""
 import numpy as np
 
 
+def _nan_max(a, b):
+    """max that keeps a NaN (np.max semantics, the reducer of flow_tools.py:32-47): Python's max(0.0, nan) is 0.0, and a
+    dropped NaN frequency would turn a blown-up velocity into the largest timestep instead of leaving dt unchanged."""
+    return a if a != a else (b if (b != b or b > a) else a)
+
+
 class GlobalFlowProperty:
     """Reductions of grid-space expressions every `cadence` iterations (flow_tools.py:49-111)."""
 
@@ -139,7 +145,7 @@ class CFL:
         fmax = 0.0
         for u in self.velocities:
             if hasattr(u, "cfl_frequency_max"):             # curvilinear fields carry their own CFL reduction
-                fmax = max(fmax, u.cfl_frequency_max())
+                fmax = _nan_max(fmax, u.cfl_frequency_max())
                 continue
             f = u if hasattr(u, "grid_data") else u.evaluate()
             inv, comp_axis, scales = self._spacings(f)

@@ -329,11 +329,16 @@ class Comm:
         return float(x.item())
 
     def allreduce_max(self, value):
+        """max over the ranks; a NaN on any rank gives NaN (np.max of the gathered values, GlobalArrayReducer of
+        extras/flow_tools.py:32-47).  What ReduceOp.MAX does with a NaN depends on the backend and the order of the
+        ranks, so the NaNs travel as a flag next to the value."""
         t = self.torch
         dev = "cuda" if (t.cuda.is_available() and self.dist.get_backend() == "nccl") else "cpu"
-        x = t.tensor([float(value)], dtype=t.float64, device=dev)
+        v = float(value)
+        x = t.tensor([float("-inf") if v != v else v, 1.0 if v != v else 0.0], dtype=t.float64, device=dev)
         self.dist.all_reduce(x, op=self.dist.ReduceOp.MAX)
-        return float(x.item())
+        mx, flag = x.tolist()
+        return float("nan") if flag else float(mx)
 
     def bcast_float(self, value, src=0):
         """rank `src`'s value on every rank (the reference's world_time broadcast, core/solvers.py:603-611)"""

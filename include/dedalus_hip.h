@@ -286,7 +286,9 @@ int ddh_ellband_bordered_inverse(const double *X_d, int n, int j0, const double 
 /* ---- grid-space and vector kernels -------------------------------- */
 /* y[idx[i]] += vals[i] for n distinct indices (device arrays): the constant right-hand-side entries
  * (e.g. "b(z=0) = Lz", gathered into F by gather_outputs core/timesteppers.py:611-614) touch a handful of
- * rows of the k = 0 pencil only. */
+ * rows of the k = 0 pencil only.  Contract of both scatter kernels: the n indices are UNIQUE and lie inside y -- one
+ * thread per entry, no atomics, no range check, so a repeated index races (the result is then unspecified) and an index
+ * outside y is an out-of-bounds access.  Entries of y that no index names are not touched; n <= 0 launches nothing. */
 int ddh_scatter_add(double *y, const long *idx_d, const double *vals_d, long n, void *stream);
 /* y[idx[i]] = vals[i]: the same entries when the right-hand-side rows are written directly by the forward transforms
  * (the constant rows of F are then set, not accumulated; core/timesteppers.py:611-614). */
@@ -316,7 +318,9 @@ int ddh_grid_bilinear(double *out, int ncomp_out, const double *a, const double 
                       const double *coef_h, void *stream);
 /* max over grid points of sum_c |u_c| / dx_c  (AdvectiveCFL core/operators.py:4342-4419 with the
  * spacings of CartesianAdvectiveCFL core/basis.py:6078-6111).  u is [ncomp][grid, naxes storage
- * axes]; inv_spacing_comp[c] is a device array of 1/dx along storage axis comp_axis_h[c].        */
+ * axes]; inv_spacing_comp[c] is a device array of 1/dx along storage axis comp_axis_h[c].  A NaN at
+ * any point makes the result NaN (f.max() of the reference, extras/flow_tools.py:199-204); the same
+ * holds for ddh_grid_cfl_spherical.                                                              */
 int ddh_grid_cfl(double *result_d, const double *u, int ncomp, long n,
                  const double *const *inv_spacing_comp, const int *comp_axis_h,
                  const long *axis_len_h, int naxes, void *stream);
