@@ -9,12 +9,14 @@ expression is split into alternating stages that each map to few large kernel la
                    term-list mat-vec over all pencils (core/polyop.py); leaves that live in the same
                    system vector (the solver state) share a launch
   backward         coefficient -> dealiased grid, one fused FFT kernel per axis
-  grid stage       products / dot / cross as a table-driven bilinear kernel
+  grid stage       products / dot / cross as a table-driven bilinear kernel; ufuncs and powers as one
+                   pointwise map kernel; operands on smaller domains broadcast by a kernel
   forward          grid -> coefficient
 
 Nothing leaves HBM between the stages.
 """
 
+import numbers
 import os
 
 import numpy as np
@@ -819,9 +821,27 @@ class Evaluator:
         src = tuple(operand.domain.storage_grid_shape(scales))
         if src == tgt:
             return g
+        if getattr(self.ex, "grid_broadcast", None) is not None:
+            present = [s == t for s, t in zip(src, tgt)]
+            if any(s != 1 for s, p in zip(src, present) if not p):
+                raise ValueError("operand grid %s does not broadcast to %s" % (src, tgt))
+            full = self.ex.empty((operand.ncomp,) + tgt)
+            self.ex.grid_broadcast(full, g, operand.ncomp, tgt, present)
+            return full
+        # an executor without grid_broadcast (the NumPy oracle of the tests): through the host
         host = self.ex.download(g).reshape((operand.ncomp,) + src)
         full = np.broadcast_to(host, (operand.ncomp,) + tgt)
         return self.ex.from_host(np.ascontiguousarray(full))
+
+    @staticmethod
+    def _map_op(func):
+        """Key of HipExecutor.MAP_OPS for a ufunc of UnaryGridFunction"""
+        from ..executor import HipExecutor
+        name = getattr(func, "__name__", None)
+        if name in ("recip", "pow") or name not in HipExecutor.MAP_OPS or func is not getattr(np, name, None):
+            raise NotImplementedError("grid function %s: only the NumPy ufuncs %s run on the device"
+                                      % (name or func, " ".join(k for k in HipExecutor.MAP_OPS if k not in ("recip", "pow"))))
+        return name
 
     def _eval_nonlinear(self, expr, scales):
         ex = self.ex
@@ -846,11 +866,21 @@ class Evaluator:
                 npts = int(np.prod(expr.domain.storage_grid_shape(scales)))
                 ex.bilinear(out, 1, ga, ga, npts, [(0, 0, 0, 1.0)])
                 return out
-            return ex.from_host(self.ex.download(ga) ** p)      # analysis-only path
+            if getattr(ex, "grid_map", None) is None:           # the NumPy oracle of the tests: through the host
+                return ex.from_host(ex.download(ga) ** p)
+            if not isinstance(p, numbers.Real):
+                raise NotImplementedError("Power with the exponent %r: constant real exponents only" % (p,))
+            out = ex.empty(self._grid_shape(expr, scales))
+            ex.grid_map(out, ga, {-1: "recip", 0.5: "sqrt"}.get(p, "pow"), p)
+            return out
         if isinstance(expr, ops.UnaryGridFunction):
             func, a = expr.args
             ga = self.eval_grid(a)
-            return ex.from_host(func(self.ex.download(ga)))     # analysis-only path
+            if getattr(ex, "grid_map", None) is None:           # the NumPy oracle of the tests: through the host
+                return ex.from_host(func(ex.download(ga)))
+            out = ex.empty(self._grid_shape(expr, scales))
+            ex.grid_map(out, ga, self._map_op(func))
+            return out
         raise NotImplementedError(type(expr))
 
     def new_pass(self):

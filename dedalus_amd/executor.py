@@ -115,6 +115,45 @@ class HipExecutor:
         libhip.call("ddh_grid_bilinear", ptr(out), ncomp_out, ptr(a), ptr(b), npts, len(terms),
                     libhip.as_ip(ic), libhip.as_ip(ia), libhip.as_ip(ib), libhip.as_dp(cf), self.dev.stream)
 
+    # ufunc.__name__ -> op of ddh_grid_map (enum ddh_map_op of include/dedalus_hip.h); "recip" and "pow" serve Power
+    MAP_OPS = {name: i for i, name in enumerate(
+        "absolute sign exp exp2 log log2 log10 sqrt square sin cos tan arcsin arccos arctan sinh cosh tanh arcsinh arccosh "
+        "arctanh recip pow".split())}
+
+    def grid_map(self, out, a, op, param=0.0):
+        """out = op(a) point by point (ddh_grid_map); op: a key of MAP_OPS, param: the exponent of "pow".  out may be a."""
+        if op not in self.MAP_OPS:
+            raise NotImplementedError("grid function %r has no device kernel" % (op,))
+        if out.numel() != a.numel() or not (out.is_contiguous() and a.is_contiguous()):
+            raise ValueError("grid_map: contiguous arrays of one size")
+        if self.timer is not None:
+            return self.timer.run("grid_map_" + op, 2 * a.numel() * 8, self._grid_map, out, a, op, param)
+        return self._grid_map(out, a, op, param)
+
+    def _grid_map(self, out, a, op, param):
+        libhip.call("ddh_grid_map", ptr(out), ptr(a), int(a.numel()), self.MAP_OPS[op], float(param), self.dev.stream)
+
+    def grid_broadcast(self, out, a, ncomp, shape, present):
+        """out[c][i0][i1][i2] = a[c][j0][j1][j2], j_k = i_k where present[k] else 0 (ddh_grid_broadcast); shape: up to three
+        storage axis lengths of out."""
+        shape, present = [int(s) for s in shape], [bool(p) for p in present]
+        if len(shape) != len(present) or len(shape) > 3:
+            raise ValueError("grid_broadcast: up to three axes")
+        shape, present = [1] * (3 - len(shape)) + shape, [False] * (3 - len(present)) + present
+        src = int(np.prod([s for s, p in zip(shape, present) if p]))
+        if (a.numel() != ncomp * src or out.numel() != ncomp * int(np.prod(shape))
+                or not (out.is_contiguous() and a.is_contiguous()) or out.data_ptr() == a.data_ptr()):
+            raise ValueError("grid_broadcast: sizes do not match shape / present")
+        if self.timer is not None:
+            return self.timer.run("grid_broadcast", (out.numel() + a.numel()) * 8, self._grid_broadcast, out, a, ncomp,
+                                  shape, present)
+        return self._grid_broadcast(out, a, ncomp, shape, present)
+
+    def _grid_broadcast(self, out, a, ncomp, shape, present):
+        sh = (C.c_long * 3)(*shape)
+        pr = (C.c_int * 3)(*[int(p) for p in present])
+        libhip.call("ddh_grid_broadcast", ptr(out), ptr(a), int(ncomp), sh, pr, self.dev.stream)
+
     FUSED_LIMITS = dict(na=3, nb=12, nc=4, terms=32, max_grid=1536)
 
     def fused_capable(self, spec):

@@ -108,6 +108,9 @@ SIGNATURES = {
     "ddh_grid_cfl": [_vp, _vp, _i, _l, C.POINTER(_vp), _ip, C.POINTER(_l), _i, _vp],
     "ddh_grid_cfl_spherical": [_vp, _vp, _l, _i, _vp, _vp, _vp],
     "ddh_grid_reduce": [_vp, _vp, _l, _vp, _vp],
+    "ddh_grid_map": [_vp, _vp, _l, _i, _d, _vp],
+    "ddh_grid_broadcast": [_vp, _vp, _i, C.POINTER(_l), _ip, _vp],
+    "ddh_grid_map_launches": [C.POINTER(_l)],
     "ddh_axis_contract": [_vp, _vp, _l, _i, _l, _l, _vp, _i, _vp],
     "ddh_pencil_create": [_hp, C.POINTER(PencilGeom)],
     "ddh_pencil_add_matrix": [_h, C.POINTER(PolyMat), _i, _ip],

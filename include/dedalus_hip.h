@@ -337,6 +337,28 @@ int ddh_grid_cfl_spherical(double *result_d, const double *u, long n_ang, int nr
 #define DDH_REDUCE_WORK_DOUBLES 3072
 int ddh_grid_reduce(double *out3_d, const double *x, long n, double *work_d, void *stream);
 
+/* out[i] = f_op(in[i], param) over n doubles: the grid-space half of UnaryGridFunction (core/operators.py:505-566: the 21
+ * NumPy ufuncs of its derivative table, func(arg['g'], out=out['g'])) and of Power with a constant exponent
+ * (core/operators.py:306-400, np.power(arg0['g'], p)).  param is read by DDH_MAP_POW only; exponents 0.5 and -1 run as
+ * sqrt and recip, integer exponents 1 <= |p| <= 8 as |p| - 1 multiplications (and one division for p < 0).  NumPy's values
+ * at special arguments: NaN in -> NaN out, out-of-domain -> NaN, log(0) = -inf, recip(+-0) = +-inf, sign(NaN) = NaN,
+ * sign(+-0) = +0 (np.sign returns +0 for both zeros), pow(negative, non-integer) = NaN.  absolute, sign, square, sqrt, recip are correctly rounded.  out == in
+ * is allowed, any other overlap is not; pointers that are not 16-byte aligned take a scalar path; n <= 0 launches nothing. */
+enum ddh_map_op {
+    DDH_MAP_ABSOLUTE = 0, DDH_MAP_SIGN, DDH_MAP_EXP, DDH_MAP_EXP2, DDH_MAP_LOG, DDH_MAP_LOG2, DDH_MAP_LOG10, DDH_MAP_SQRT,
+    DDH_MAP_SQUARE, DDH_MAP_SIN, DDH_MAP_COS, DDH_MAP_TAN, DDH_MAP_ARCSIN, DDH_MAP_ARCCOS, DDH_MAP_ARCTAN, DDH_MAP_SINH,
+    DDH_MAP_COSH, DDH_MAP_TANH, DDH_MAP_ARCSINH, DDH_MAP_ARCCOSH, DDH_MAP_ARCTANH, DDH_MAP_RECIP, DDH_MAP_POW
+};
+int ddh_grid_map(double *out, const double *in, long n, int op, double param, void *stream);
+/* out[c][i0][i1][i2] = in[c][j0][j1][j2], j_k = present[k] ? i_k : 0, over the storage axes shape[3] of the output: an
+ * operand that lacks some bases of a product's domain (a z profile times a full field) expanded to the full grid -- the
+ * NumPy broadcasting of MultiplyFields.operate (core/arithmetic.py:666-674).  `in` holds ncomp contiguous blocks of the
+ * product of the present axis lengths.  Out of place.                                                                */
+int ddh_grid_broadcast(double *out, const double *in, int ncomp, const long *shape_h, const int *present_h, void *stream);
+/* Diagnostic: launches of the two kernels above by this process (as ddh_fft_wave_launches: tests assert that an
+ * expression ran here and not through the host).                                                                      */
+int ddh_grid_map_launches(long *count);
+
 /* Contraction of one storage axis with nw (1..4) weight vectors, the device half of reduced analysis tasks:
  *   in [outer][n][inner] with the blocks of one `outer` index ostride (>= n * inner) doubles apart, w [nw][n]
  *   out[o][j][i] = sum_k w[j][k] * in[o][k][i],   out [outer][nw][inner] contiguous.
