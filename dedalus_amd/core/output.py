@@ -124,9 +124,9 @@ def _scale_tuple(scales, n):
 def _describe(dist, field, layout, data):
     """-> (axes, constant flags, scales, shard axis) with axes = [(scale name, coordinate data or None)] per spatial axis
     of the GLOBAL user array and shard axis = index (among ALL axes of `data`) along which ranks hold blocks"""
-    from . import shell as _shell, sphere as _sphere
+    from . import shell as _shell, sphere as _sphere, sphreduce as _sphreduce
     grid = layout == 'g'
-    if isinstance(field, (_shell.ShellField, _sphere.SField, _shell.ShAzimuthalInterp)):
+    if isinstance(field, (_shell.ShellField, _sphere.SField, _sphreduce.ReducedResult)):
         basis = field.basis
         names = [c.name if hasattr(c, "name") else str(c) for c in dist.coords]
         dim = len(names)

@@ -21,7 +21,7 @@ import time as _time
 import numpy as np
 
 from ..tools import sphere as sph
-from . import curvilinear
+from . import curvilinear, sphreduce
 from .basis import Jacobi
 from .coords import Coordinate
 from .ivp_common import IVPLifecycle
@@ -47,6 +47,9 @@ class SphericalCoordinates:
 
     def __iter__(self):
         return iter(self.coords)
+
+    def __getitem__(self, name):
+        return self.coords[self.names.index(name)]
 
     @staticmethod
     def U_forward(order=1):
@@ -186,6 +189,33 @@ class ShellBasis:
             slot = np.ascontiguousarray(slot[2 * sb.m0:2 * (sb.m0 + sb.nml)])
             store[key] = (ex.make_recombination(slot, fwd) if rank > 0 else None,
                           ex.make_recombination(slot, bwd) if rank > 0 else None)
+        return store[key]
+
+    def zonal_plans(self, ex, Ntheta_g, rank):
+        """The m = 0 rows of colatitude_plan and of the backward regularity_plan, for data [nc][2][nl][Nr_g] (zonal
+        means): (grouped SWSH plan, Q(ell) table or None)."""
+        key = ("zonal", id(ex), Ntheta_g, rank)
+        store = getattr(self, "_root", self)._plans
+        if key not in store:
+            sb = self.sphere
+            groups, keys, fwd, bwd = [], [], [], []
+            for i, s in enumerate(self.spin_totals(rank)):
+                mk = 4096 * (s + 8)
+                groups.append((mk, 2 * i, 2 * i, 2, 0, 1, sb.Lmax + 1))
+                if mk not in keys:
+                    f, b = sph.swsh_matrices(Ntheta_g, sb.Lmax, 0, s)
+                    keys.append(mk)
+                    fwd.append(f)
+                    bwd.append(b)
+            plan = ex.make_grouped_mmt(Ntheta_g, np.array(groups, dtype=np.int64), keys, fwd, bwd)
+            table = None
+            if rank > 0:
+                slot_p, _, bwd_q = curvilinear.recombination_tables(sb.packed_ell_rows(), sb.packed_shape(), rank)
+                rows, cols, ok = sb.pack_index()
+                slot = -np.ones((2 * sb.nm, sb.nl), dtype=np.int32)
+                slot[rows[ok], cols[ok]] = slot_p[ok]
+                table = ex.make_recombination(np.ascontiguousarray(slot[0:2]), bwd_q)
+            store[key] = (plan, table)
         return store[key]
 
     def radial_factor(self, ex, scale, power):
@@ -330,11 +360,13 @@ def _radial_gemm(dist, basis, scale, nc, forward_dir):
     return basis._plans[key]
 
 
-def backward(dist, basis, rank, c, scales):
+def backward(dist, basis, rank, c, scales, upto=None):
     """coefficients [nc][2 nml][nl][Nr] (regularity components, local m) -> grid [nc][Nphi_g][Ntheta_g / P][Nr_g]
     (coordinate components, local colatitudes).  On P ranks the only exchange is the all-to-all between "m local
     block, all colatitudes" and "all m, colatitude block" that replaces the reference's (azimuth, colatitude)
-    transpose (core/distributor.py:770-924), placed before the azimuthal FFT."""
+    transpose (core/distributor.py:770-924), placed before the azimuthal FFT.
+    upto (reduced analysis tasks): "spin" stops at the spin components [nc][2 nml][nl][Nr_g], "azimuth" at the coordinate
+    components [nc][2 nm][Ntheta_g / P * Nr_g] in front of the azimuthal FFT (all m local)."""
     ex = dist.executor
     sb = basis.sphere
     nc = 3 ** rank
@@ -352,6 +384,8 @@ def backward(dist, basis, rank, c, scales):
             ex.transform(basis.radial.plan_spec(scales[2]), basis.radial, "backward", c, t0, nslots, 1)
         ex.regularity_recombine(t0, basis.regularity_plan(ex, rank)[1],
                                 basis.radial_factor(ex, scales[2], basis.k) if basis.k > 0 else None)
+    if upto == "spin":
+        return t0
     t1 = ex.empty((nc, 2 * nml, Nt, Ng))
     basis.colatitude_plan(ex, Nt, rank).backward(t0.reshape(1, nc * 2 * nml, sb.nl, Ng),
                                                  t1.reshape(1, nc * 2 * nml, Nt, Ng))
@@ -371,12 +405,15 @@ def backward(dist, basis, rank, c, scales):
         dist.pcomm.all_to_all(recv, send)
         t2 = ex.empty((nc, 2 * sb.nm, Ntl * Ng))
         ex.a2a_unpack(recv, t2, nc, 1, 2 * nml * P, Ntl * Ng, P)
+    if upto == "azimuth":
+        return t2
     g = ex.empty((nc, Np, Ntl, Ng))
     ex.transform(("rfft", Np, sb.Nphi), None, "backward", t2, g, nc, Ntl * Ng)
     return g
 
 
-def forward(dist, basis, rank, g, scales):
+def forward(dist, basis, rank, g, scales, upto=None):
+    """the mirror of backward; upto "azimuth" / "spin" stop at the same two stages"""
     ex = dist.executor
     sb = basis.sphere
     nc = 3 ** rank
@@ -386,6 +423,8 @@ def forward(dist, basis, rank, g, scales):
     Ntl = dist.theta_range(Nt)[1] if P > 1 else Nt
     t1 = ex.empty((nc, 2 * sb.nm, Ntl * Ng))
     ex.transform(("rfft", Np, sb.Nphi), None, "forward", g, t1, nc, Ntl * Ng)
+    if upto == "azimuth":
+        return t1
     if P > 1:
         # [nc][2 nm][Nt / P][Ng] -> [nc][2 nml][Nt][Ng]
         n_el = nc * 2 * sb.nm * Ntl * Ng
@@ -402,7 +441,7 @@ def forward(dist, basis, rank, g, scales):
     t3 = ex.zeros((nc, 2 * nml, sb.nl, Ng))
     basis.colatitude_plan(ex, Nt, rank).forward(t2.reshape(1, nc * 2 * nml, Nt, Ng),
                                                 t3.reshape(1, nc * 2 * nml, sb.nl, Ng))
-    if isinstance(basis, SurfaceBasis):
+    if isinstance(basis, SurfaceBasis) or upto == "spin":
         return t3
     ex.regularity_recombine(t3, basis.regularity_plan(ex, rank)[0],
                             basis.radial_factor(ex, scales[2], -basis.k) if basis.k > 0 else None)
@@ -707,6 +746,8 @@ class ShOperand:
         (name, pos), = kw.items()
         if name == self.dist.coordsys.coords[0].name:
             return ShAzimuthalInterp(self, float(pos))
+        if name == self.dist.coordsys.colatitude.name:
+            return ShColatitudeInterp(self, float(pos))
         if name != self.dist.coordsys.radius.name:
             return ShUnsupported("interpolation along %r" % name, self)
         return ShLinear("interp", self, position=float(pos))
@@ -724,52 +765,184 @@ class ShOperand:
         return f
 
 
-class ShAzimuthalInterp(ShOperand):
-    """f(phi=phi0) (core/operators.py interpolate dispatch -> SphereBasis azimuthal interpolation): an ANALYSIS-ONLY
-    operand (output tasks such as the example's meridional flux slices).  The operand is evaluated on the grid at the
-    requested scales and its trigonometric interpolant along phi is evaluated on the host; the result keeps a phi
-    axis of size one (a constant axis in the output file)."""
+class ShReduced(sphreduce.ReducedResult, ShOperand):
+    """Reduced analysis tasks of shell operands (core/sphreduce.py): contractions of the stages backward() / forward()
+    produce, on the device; ['g'] downloads the reduced result only."""
 
-    const_axes = (0,)
+    dim = 3
+    from_grid = False
 
-    def __init__(self, arg, position):
-        self.args, self.position = (arg,), position
-        self.dist, self.basis, self.rank = arg.dist, arg.basis, arg.rank
-        self.scales = (1.0, 1.0, 1.0)
-        self._field = None
+    def __init__(self, arg, **params):
+        if not isinstance(arg, ShOperand) or isinstance(arg, (RadialField, ConstField)) or arg.basis is None:
+            raise NotImplementedError("%s of an operand without an angular basis" % self.what)
+        if isinstance(arg, ShLinear) and arg.kind in ("interp", "integ"):
+            raise NotImplementedError("%s of a reduced operand (%s): reductions of reductions are not supported"
+                                      % (self.what, arg.kind))
+        self._init(arg, **params)
 
-    def evaluate(self):
-        out = ShAzimuthalInterp(self.args[0], self.position)
-        arg = self.args[0]
-        out._field = arg if isinstance(arg, ShellField) else arg.evaluate()
-        return out
+    @property
+    def field_type(self):
+        return ShellField
 
-    def require_coeff_space(self):
-        self._field.require_coeff_space()
+    def _native_grid(self, arg):
+        return arg.grid_native()
 
-    def change_scales(self, scales):
-        self.scales = self._field._remedy(scales)
+    def _field_from_grid(self, g):
+        f = ShellField(self.dist, self.basis, rank=self.rank)
+        f._set_device_coeff(forward(self.dist, self.basis, self.rank, g, self.basis.dealias))
+        return f
 
-    def __getitem__(self, layout):
-        if layout not in ("g", "grid"):
-            raise NotImplementedError("coefficient data of an azimuthal interpolation")
-        f = self._field
-        f.change_scales(self.scales)
-        g = np.asarray(f["g"])
-        ax = self.rank
-        Np = g.shape[ax]
-        c = np.fft.rfft(g, axis=ax) / Np
-        k = np.arange(c.shape[ax])
-        w = np.where((k == 0) | ((Np % 2 == 0) & (k == Np // 2)), 1.0, 2.0) * np.exp(1j * k * self.position)
-        shape = [1] * g.ndim
-        shape[ax] = k.size
-        return np.sum((c * w.reshape(shape)).real, axis=ax, keepdims=True)
+    def _tensor_shape(self):
+        return (3,) * self.rank
 
-    def eval_c(self):
-        raise NotImplementedError("azimuthal interpolation is an output task, not a term of an equation")
+    def _store(self):
+        b = self.basis.shell if isinstance(self.basis, SurfaceBasis) else self.basis
+        return getattr(b, "_root", b)._plans
+
+    def _single_rank(self):
+        if self.dist.size > 1:
+            raise NotImplementedError("%s on several ranks: the azimuthal wavenumbers are distributed where it is formed"
+                                      % self.what)
 
     def lin(self, variables):
-        raise NonlinearError("azimuthal interpolation in an equation")
+        raise NonlinearError("%s in an equation" % self.what)
+
+
+class ShAzimuthalInterp(ShReduced):
+    """f(phi=phi0) (InterpolateAzimuth, core/basis.py:5578-5634): the coordinate components in front of the azimuthal FFT,
+    [nc][2 nm][colatitudes * radii] with all m local (on several ranks: after the m <-> theta exchange), contracted with
+    cos m phi0, -sin m phi0 in one ddh_axis_contract launch.  The result keeps a phi axis of size one."""
+
+    what = "azimuthal interpolation"
+    const_axes = (0,)
+    from_grid = True
+
+    def __init__(self, arg, position):
+        ShReduced.__init__(self, arg, position=float(position))
+        self.position = float(position)
+
+    def _init(self, arg, **params):
+        ShReduced._init(self, arg, **params)
+        self.position = params["position"]
+
+    def _device(self, scales):
+        ex, sb = self.dist.executor, self.basis.sphere
+        nc = self.ncomp
+        if self._grid is not None and scales == tuple(self.basis.dealias):
+            t = forward(self.dist, self.basis, self.rank, self._grid, scales, upto="azimuth")
+        else:
+            t = backward(self.dist, self.basis, self.rank, self._coeff_field().require_coeff_space(), scales, upto="azimuth")
+        Np, Nt, Ng = self.basis.grid_shape(scales)
+        Ntl = self.dist.theta_range(Nt)[1]
+        out = sphreduce.contract(ex, self._store(), t, nc, 2 * sb.nm, Ntl * Ng, sphreduce.azimuth_weights(sb.nm, self.position))
+        return out.reshape(nc, 1, Ntl, Ng)
+
+
+class ShColatitudeInterp(ShReduced):
+    """f(theta=theta0) (InterpolateColatitude, core/basis.py:5637-5736): the spin components [nc][2 nml][nl][Nr_g]
+    contracted along ell with Y_l^{m,s}(theta0) (ddh_axis_contract_rows: one weight row per (spin weight, m), read from
+    l = max(m, |s|) on), then the spin recombination and the azimuthal FFT of backward() on [nc][2 nm][Nr_g]."""
+
+    what = "colatitude interpolation"
+    const_axes = (1,)
+    from_grid = True
+
+    def __init__(self, arg, position):
+        ShReduced.__init__(self, arg, position=float(position))
+
+    def _init(self, arg, **params):
+        ShReduced._init(self, arg, **params)
+        self.position = params["position"]
+
+    def _device(self, scales):
+        self._single_rank()
+        ex, basis, rank = self.dist.executor, self.basis, self.rank
+        sb = basis.sphere
+        nc, nml = self.ncomp, sb.nml
+        if self._grid is not None and scales == tuple(basis.dealias):
+            t0 = forward(self.dist, basis, rank, self._grid, scales, upto="spin")
+        else:
+            t0 = backward(self.dist, basis, rank, self._coeff_field().require_coeff_space(), scales, upto="spin")
+        Np, Nt, Ng = basis.grid_shape(scales)
+        t1 = sphreduce.contract_rows(ex, self._store(), ("theta", rank, self.position), t0, nc * 2 * nml, sb.nl, Ng,
+                                     lambda: sphreduce.colatitude_rows(sb, basis.spin_totals(rank), sb.m0, nml, self.position))
+        t1 = t1.reshape(nc, 2 * nml, Ng)
+        if rank > 0:
+            t2 = ex.empty((nc, 2 * nml, Ng))
+            ex.spin_recombine(t1, t2, basis.recombination_matrix(rank, forward=False))
+        else:
+            t2 = t1
+        g = ex.empty((nc, Np, 1, Ng))
+        ex.transform(("rfft", Np, sb.Nphi), None, "backward", t2, g, nc, Ng)
+        return g
+
+
+class ShAzimuthalAverage(ShReduced):
+    """ave(f, phi) (SphericalAzimuthalAverage, core/basis.py:5267-5293: the m = 0 coefficients): the m = 0 slab of the
+    coefficient data, gathered by pointer and stride, through the radial and colatitude backward transforms and the spin
+    recombination on its own; no FFT."""
+
+    what = "zonal mean"
+    const_axes = (0,)
+
+    def __init__(self, arg):
+        ShReduced.__init__(self, arg)
+
+    def _device(self, scales):
+        self._single_rank()
+        ex, basis, rank, store = self.dist.executor, self.basis, self.rank, self._store()
+        sb = basis.sphere
+        nc, nl, Nr = self.ncomp, sb.nl, basis.Nr
+        Np, Nt, Ng = basis.grid_shape(scales)
+        one = np.ones((1, 1))
+        c = self._coeff_field().require_coeff_space()
+        c0 = sphreduce.contract(ex, store, c, nc, 1, 2 * nl * Nr, one, ostride=sb.nml * 2 * nl * Nr).reshape(nc, 2, nl, Nr)
+        plan, table = basis.zonal_plans(ex, Nt, rank)
+        if isinstance(basis, SurfaceBasis):
+            t0 = c0
+        else:
+            t0 = ex.empty((nc, 2, nl, Ng))
+            ex.transform(basis.radial.plan_spec(scales[2]), basis.radial, "backward", c0, t0, nc * 2 * nl, 1)
+            ex.regularity_recombine(t0, table, basis.radial_factor(ex, scales[2], basis.k) if basis.k > 0 else None)
+        t1 = ex.empty((nc, 2, Nt, Ng))
+        plan.backward(t0.reshape(1, nc * 2, nl, Ng), t1.reshape(1, nc * 2, Nt, Ng))
+        if rank > 0:
+            t2 = ex.empty((nc, 2, Nt * Ng))
+            ex.spin_recombine(t1.reshape(nc, 2, Nt * Ng), t2, basis.recombination_matrix(rank, forward=False))
+        else:
+            t2 = t1
+        out = sphreduce.contract(ex, store, t2, nc, 1, Nt * Ng, one, ostride=2 * Nt * Ng)     # the cos part of m = 0
+        return out.reshape(nc, 1, Nt, Ng)
+
+
+class ShSphereAverage(ShReduced):
+    """ave(f, S2) of a scalar (SphericalAverage, core/basis.py:5321-5350: the ell = 0 coefficients): the (m, ell) = (0, 0)
+    line of the coefficient data through the radial backward transform, times Y_00 -- a radial profile."""
+
+    what = "shell average"
+    const_axes = (0, 1)
+
+    def __init__(self, arg):
+        if getattr(arg, "rank", 0):
+            raise NotImplementedError("shell average of a tensor")
+        ShReduced.__init__(self, arg)
+        if not isinstance(self.basis, ShellBasis):
+            raise NotImplementedError("shell average of an operand without a shell basis")
+
+    def _device(self, scales):
+        self._single_rank()
+        ex, basis = self.dist.executor, self.basis
+        Ng = basis.grid_shape(scales)[2]
+        c = self._coeff_field().require_coeff_space()
+        line = ex.empty((1, 1, 1, basis.Nr))
+        ex.assign(line, c[0:1, 0:1, 0:1, :])
+        t0 = ex.empty((1, 1, 1, Ng))
+        ex.transform(basis.radial.plan_spec(scales[2]), basis.radial, "backward", line, t0, 1, 1)
+        if basis.k > 0:
+            ex.regularity_recombine(t0, None, basis.radial_factor(ex, scales[2], basis.k))
+        out = ex.empty((1, 1, 1, Ng))
+        ex.lincomb(out, [t0], [float(sph.harmonics(0, 0, 0, 0.0)[0, 0])])
+        return out
 
 
 class ShUnsupported(ShOperand):
@@ -1161,6 +1334,28 @@ def trace(a):
 
 def integ(a, *coords):
     return ShLinear("integ", a)
+
+
+def ave(a, *coords):
+    """Average(f, coords['phi']) -> zonal mean; Average(f, coords.S2coordsys) or ave(f) -> the average over the spheres
+    r = const, a radial profile.  Coordinates by object or by name, as the reference accepts them."""
+    if len(coords) == 1 and isinstance(coords[0], (tuple, list)):
+        coords = tuple(coords[0])
+    cs = a.dist.coordsys
+    if isinstance(a, ShReduced):
+        raise NotImplementedError("average of a reduced operand (%s): reductions of reductions are not supported" % a.what)
+    if not coords:
+        return ShSphereAverage(a)
+    names = [c if isinstance(c, str) else getattr(c, "name", None) for c in coords]
+    if len(coords) == 1 and (coords[0] is cs.azimuth or names[0] == cs.azimuth.name):
+        return ShAzimuthalAverage(a)
+    if (len(coords) == 1 and isinstance(coords[0], S2Coordinates)) or \
+            (len(coords) == 2 and set(names) == {cs.azimuth.name, cs.colatitude.name}):
+        return ShSphereAverage(a)
+    raise NotImplementedError("average of a shell operand over %r" % (coords,))
+
+
+Average = ave
 
 
 def grad(a):
@@ -1558,7 +1753,7 @@ class ShellProblem:
         self.equations = []
         self.namespace = dict(lap=lap, grad=grad, div=div, dt=dt, Lift=Lift, lift=Lift, trace=trace, integ=integ,
                               Laplacian=lap, Gradient=grad, Divergence=div, TimeDerivative=dt, Trace=trace,
-                              Integrate=integ, np=np, numpy=np)
+                              Integrate=integ, ave=ave, Average=ave, np=np, numpy=np)
         if namespace:
             self.namespace.update(namespace)
         for v in self.variables:

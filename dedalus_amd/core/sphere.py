@@ -33,6 +33,7 @@ import numpy as np
 
 from ..tools import jacobi
 from ..tools import sphere as sph
+from . import sphreduce
 from .coords import Coordinate
 from .ivp_common import IVPLifecycle
 
@@ -56,6 +57,9 @@ class S2Coordinates:
 
     def __iter__(self):
         return iter(self.coords)
+
+    def __getitem__(self, name):
+        return self.coords[self.names.index(name)]
 
     @staticmethod
     def U_forward(order=1):
@@ -516,6 +520,18 @@ class SOperand:
     def __matmul__(self, other):
         return SDot(self, other)
 
+    def __call__(self, **kw):
+        """f(phi=phi0), f(theta=theta0): interpolation along one coordinate (output tasks)."""
+        if len(kw) != 1:
+            raise ValueError("one coordinate at a time")
+        (name, pos), = kw.items()
+        cs = self.dist.coordsys
+        if name == cs.azimuth.name:
+            return SAzimuthalInterp(self, float(pos))
+        if name == cs.colatitude.name:
+            return SColatitudeInterp(self, float(pos))
+        raise ValueError("no coordinate %r on the sphere" % name)
+
     @property
     def ncomp(self):
         return 2 ** self.rank
@@ -543,7 +559,8 @@ def _ex(dist):
     return dist.executor
 
 
-def _backward(dist, basis, rank, c, scales):
+def _backward(dist, basis, rank, c, scales, upto=None):
+    """upto "azimuth" (reduced analysis tasks): stop at the coordinate components [nc][2 nm][Nt] in front of the FFT"""
     ex = _ex(dist)
     nc = 2 ** rank
     Np, Nt = basis.grid_shape(scales)
@@ -555,17 +572,21 @@ def _backward(dist, basis, rank, c, scales):
         ex.spin_recombine(t1, t2, basis.recombination_matrix(rank, forward=False))
     else:
         t2 = t1
+    if upto == "azimuth":
+        return t2
     g = ex.empty((nc, Np, Nt))
     ex.transform(("rfft", Np, basis.Nphi), None, "backward", t2, g, nc, Nt)
     return g
 
 
-def _forward(dist, basis, rank, g, scales):
+def _forward(dist, basis, rank, g, scales, upto=None):
     ex = _ex(dist)
     nc = 2 ** rank
     Np, Nt = basis.grid_shape(scales)
     t1 = ex.empty((nc, 2 * basis.nm, Nt))
     ex.transform(("rfft", Np, basis.Nphi), None, "forward", g, t1, nc, Nt)
+    if upto == "azimuth":
+        return t1
     if rank > 0:
         t2 = ex.empty((nc, 2 * basis.nm, Nt))
         ex.spin_recombine(t1, t2, basis.recombination_matrix(rank, forward=True))
@@ -978,6 +999,130 @@ class SDot(SProduct):
     contract = True
 
 
+# ---- reduced analysis tasks (core/sphreduce.py) ----------------------------------------------------------------------
+
+class SReduced(sphreduce.ReducedResult, SOperand):
+    """Slices and zonal means of sphere operands: contractions of the coefficient data [comp][2 m + part][ell] (contiguous
+    lines along ell: the one-wavefront-per-line regime of the two kernels) on the device."""
+
+    dim = 2
+
+    def __init__(self, arg, **params):
+        if not isinstance(arg, SOperand) or arg.basis is None or getattr(arg, "is_constant", False):
+            raise NotImplementedError("%s of an operand without a sphere basis" % self.what)
+        self._init(arg, **params)
+
+    def _init(self, arg, **params):
+        sphreduce.ReducedResult._init(self, arg, **params)
+        self.position = params.get("position")
+
+    @property
+    def field_type(self):
+        return SField
+
+    def _native_grid(self, arg):
+        return arg.eval_g() if isinstance(arg, SProduct) else None
+
+    def _field_from_grid(self, g):
+        f = SField(self.dist, basis=self.basis, rank=self.rank)
+        f._set_device_coeff(_forward(self.dist, self.basis, self.rank, g, self.basis.dealias))
+        return f
+
+    def _tensor_shape(self):
+        return (2,) * self.rank
+
+    def lin(self, variables, basis):
+        raise NonlinearError("%s in an equation" % self.what)
+
+
+class SAzimuthalInterp(SReduced):
+    """f(phi=phi0) (InterpolateAzimuth, core/basis.py:5578-5634) -> (..., 1, Ntheta_g)"""
+
+    what = "azimuthal interpolation"
+    const_axes = (0,)
+    from_grid = True
+
+    def __init__(self, arg, position):
+        SReduced.__init__(self, arg, position=float(position))
+
+    def _device(self, scales):
+        ex, basis, nc = _ex(self.dist), self.basis, self.ncomp
+        Np, Nt = basis.grid_shape(scales)
+        if self._grid is not None and scales == tuple(basis.dealias):
+            t = _forward(self.dist, basis, self.rank, self._grid, scales, upto="azimuth")
+        else:
+            t = _backward(self.dist, basis, self.rank, self._coeff_field().require_coeff_space(), scales, upto="azimuth")
+        out = sphreduce.contract(ex, basis._plans, t, nc, 2 * basis.nm, Nt, sphreduce.azimuth_weights(basis.nm, self.position))
+        return out.reshape(nc, 1, Nt)
+
+
+class SColatitudeInterp(SReduced):
+    """f(theta=theta0) (InterpolateColatitude, core/basis.py:5637-5736) -> (..., Nphi_g, 1): the coefficient data (spin
+    components) contracted along ell with Y_l^{m,s}(theta0), spin recombination, azimuthal FFT."""
+
+    what = "colatitude interpolation"
+    const_axes = (1,)
+
+    def __init__(self, arg, position):
+        SReduced.__init__(self, arg, position=float(position))
+
+    def _device(self, scales):
+        ex, basis, rank, nc = _ex(self.dist), self.basis, self.rank, self.ncomp
+        Np, Nt = basis.grid_shape(scales)
+        c = self._coeff_field().require_coeff_space()
+        t1 = sphreduce.contract_rows(ex, basis._plans, ("theta", rank, self.position), c, nc * 2 * basis.nm, basis.nl, 1,
+                                     lambda: sphreduce.colatitude_rows(basis, basis.spin_totals(rank), 0, basis.nm, self.position))
+        t1 = t1.reshape(nc, 2 * basis.nm, 1)
+        if rank > 0:
+            t2 = ex.empty((nc, 2 * basis.nm, 1))
+            ex.spin_recombine(t1, t2, basis.recombination_matrix(rank, forward=False))
+        else:
+            t2 = t1
+        g = ex.empty((nc, Np, 1))
+        ex.transform(("rfft", Np, basis.Nphi), None, "backward", t2, g, nc, 1)
+        return g
+
+
+class SAzimuthalAverage(SReduced):
+    """ave(f, phi) (SphereAzimuthalAverage, core/basis.py:5238-5264: the m = 0 coefficients) -> (..., 1, Ntheta_g): the
+    m = 0 slab gathered by pointer and stride, its colatitude transform and spin recombination alone; no FFT."""
+
+    what = "zonal mean"
+    const_axes = (0,)
+
+    def __init__(self, arg):
+        SReduced.__init__(self, arg)
+
+    def _device(self, scales):
+        ex, basis, rank, nc = _ex(self.dist), self.basis, self.rank, self.ncomp
+        Np, Nt = basis.grid_shape(scales)
+        nl = basis.nl
+        one = np.ones((1, 1))
+        c = self._coeff_field().require_coeff_space()
+        c0 = sphreduce.contract(ex, basis._plans, c, nc, 1, 2 * nl, one, ostride=basis.nm * 2 * nl)
+        key = ("zonal", id(ex), Nt, rank)
+        if key not in basis._plans:
+            groups, keys, fwd, bwd = [], [], [], []
+            for i, sv in enumerate(basis.spin_totals(rank)):
+                mk = 4096 * (sv + 8)
+                groups.append((mk, 2 * i, 2 * i, 2, 0, 1, basis.Lmax + 1))
+                if mk not in keys:
+                    f, b = sph.swsh_matrices(Nt, basis.Lmax, 0, sv)
+                    keys.append(mk)
+                    fwd.append(f)
+                    bwd.append(b)
+            basis._plans[key] = ex.make_grouped_mmt(Nt, np.array(groups, dtype=np.int64), keys, fwd, bwd)
+        t1 = ex.empty((nc, 2, Nt))
+        basis._plans[key].backward(c0.reshape(1, nc * 2, nl, 1), t1.reshape(1, nc * 2, Nt, 1))
+        if rank > 0:
+            t2 = ex.empty((nc, 2, Nt))
+            ex.spin_recombine(t1, t2, basis.recombination_matrix(rank, forward=False))
+        else:
+            t2 = t1
+        out = sphreduce.contract(ex, basis._plans, t2, nc, 1, Nt, one, ostride=2 * Nt)        # the cos part of m = 0
+        return out.reshape(nc, 1, Nt)
+
+
 # ---- user-facing operator functions ------------------------------------------------------------------------------
 
 def grad(a):
@@ -1003,6 +1148,15 @@ def MulCosine(a):
 
 
 def ave(a, *coords):
+    """ave(f) / Average(f, S2 coordinates): the constant; Average(f, coords['phi']) or ave(f, 'phi'): the zonal mean"""
+    if len(coords) == 1 and isinstance(coords[0], (tuple, list)):
+        coords = tuple(coords[0])
+    if isinstance(a, SReduced):
+        raise NotImplementedError("average of a reduced operand (%s): reductions of reductions are not supported" % a.what)
+    if len(coords) == 1 and isinstance(a, SOperand):
+        az = a.dist.coordsys.azimuth
+        if coords[0] is az or coords[0] == az.name:
+            return SAzimuthalAverage(a)
     return SAverage(a)
 
 

@@ -397,6 +397,21 @@ class HipExecutor:
                     self.dev.stream)
         return out
 
+    def from_host_int32(self, a):
+        return self.torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32), device=self.dev.tdev)
+
+    def axis_contract_rows(self, x, outer, n, inner, w, rows, kmin):
+        """out[o][i] = sum_{k >= kmin[rows[o]]} w[rows[o]][k] x[o][k][i] for contiguous x = [outer][n][inner] device data,
+        w = [nrows][n] device weights, rows = [outer] / kmin = [nrows] device int32 -> [outer][inner]
+        (ddh_axis_contract_rows).  Entries below kmin are not read (bytes: half of x for triangular truncation)."""
+        nrows = int(w.shape[0])
+        x = x if x.is_contiguous() else x.contiguous()
+        out = self.empty((int(outer), int(inner)))
+        libhip.note_cost("ddh_axis_contract_rows", 2.0 * outer * n * inner, 8.0 * outer * inner * (n + 1))
+        libhip.call("ddh_axis_contract_rows", ptr(x), ptr(out), int(outer), int(n), int(inner), ptr(w),
+                    C.c_void_p(rows.data_ptr()), C.c_void_p(kmin.data_ptr()), nrows, self.dev.stream)
+        return out
+
     def a2a_plan(self, pcomm, n0, n1, n2, n3):
         """Library-owned transpose plan (ddh_a2a_plan on the RCCL communicator of `pcomm`), cached per shape; None when
         the exchange goes through torch.distributed (parallel.Comm.library_comm)."""

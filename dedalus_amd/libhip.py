@@ -112,6 +112,7 @@ SIGNATURES = {
     "ddh_grid_broadcast": [_vp, _vp, _i, C.POINTER(_l), _ip, _vp],
     "ddh_grid_map_launches": [C.POINTER(_l)],
     "ddh_axis_contract": [_vp, _vp, _l, _i, _l, _l, _vp, _i, _vp],
+    "ddh_axis_contract_rows": [_vp, _vp, _l, _i, _l, _vp, _vp, _vp, _i, _vp],
     "ddh_pencil_create": [_hp, C.POINTER(PencilGeom)],
     "ddh_pencil_add_matrix": [_h, C.POINTER(PolyMat), _i, _ip],
     "ddh_pencil_matvec": [_h, _i, _vp, _vp, _vp],

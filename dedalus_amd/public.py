@@ -49,6 +49,7 @@ def _dispatch(name, cart):
 grad, div, lap, skew, ave, dt, trace, integ = (_dispatch(n, c) for n, c in (
     ("grad", grad), ("div", div), ("lap", lap), ("skew", skew), ("ave", ave), ("dt", dt), ("trace", trace),
     ("integ", integ)))
+Average = _dispatch("ave", Average)          # Average(f, coords['phi']) of sphere / shell operands; else the Cartesian class
 MulCosine = _sphere.MulCosine
 _CartesianIVP, _CartesianLBVP = IVP, LBVP
 

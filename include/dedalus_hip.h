@@ -368,6 +368,16 @@ int ddh_grid_map_launches(long *count);
  * n alone), no atomics: repeated calls are bit-identical; NaN-propagating.                                          */
 int ddh_axis_contract(const double *in_d, double *out_d, long outer, int n, long inner, long ostride,
                       const double *w_d, int nw, void *stream);
+/* The same contraction with a weight vector and a first entry that depend on the outer index:
+ *   in [outer][n][inner] contiguous, w [nrows][n], row [outer] (device ints in 0 .. nrows - 1), kmin [nrows] (0 .. n)
+ *   out[o][i] = sum_{k = kmin[row[o]]}^{n-1} w[row[o]][k] * in[o][k][i],   out [outer][inner] contiguous.
+ * Interpolation along the colatitude (InterpolateColatitude, core/basis.py: the spin-weighted harmonics
+ * Y_l^{m,s}(theta0) differ per (spin component, m) and only l >= max(m, |s|) carries data): entries below kmin are
+ * never read, every entry from kmin on is (NaN-propagating, no early-out on zero weights), kmin == n gives +0.  Fixed
+ * summation order (a function of (n, kmin) alone), no atomics: repeated calls and every launch shape give the same
+ * bits.  A row index outside 0 .. nrows - 1 reads nothing and writes NaN.                                             */
+int ddh_axis_contract_rows(const double *in_d, double *out_d, long outer, int n, long inner, const double *w_d,
+                           const int *row_d, const int *kmin_d, int nrows, void *stream);
 
 /* ---- pencil systems ------------------------------------------ */
 /* A "pencil pack" describes all pencils of a problem at once.  System vectors are real arrays
