@@ -256,7 +256,7 @@ class EllBandPlan:
         r[:k] = self.T[g, :k, :k] @ r[:k]
         y, info = lapack.dgbtrs(lu, kl, ku, r, piv)
         z = y.copy()
-        for s in range(self.mp):
+        for s in range(min(self.mp, n - 1)):                           # (a system shorter than the band of P has fewer)
             z[:n - 1 - s] += self.P[g, :n - 1 - s, s, None] * y[1 + s:]
         out = np.zeros_like(rhs_flat, dtype=float)
         out[self.col_index[g, :n]] = z

@@ -65,6 +65,8 @@ def test_band_plan_rejects_what_it_cannot_band():
 @pytest.mark.gpu
 @pytest.mark.parametrize("shape", [(16, 8, 32), (32, 16, 24)])
 def test_device_band_lu_of_the_shell_systems_against_dense_solves(shape):
+    """the kernels inside a whole shell solver, at the tolerance its cond ~ 1e8 systems allow; the kernels on their own, at
+    every compiled window and at rounding-level bounds: tests/test_gpu_ellband_kernels.py"""
     import dedalus_amd.public as d3
     s, _ = problems.shell_convection(d3, shape=shape)
     assert s.ex.name == "hip"
