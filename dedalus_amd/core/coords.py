@@ -19,6 +19,25 @@ class Coordinate:
             raise ValueError("bounds must be (lower, upper) with upper > lower")
 
 
+class SpinCoordinates:
+    """What S2Coordinates (core/sphere.py) and SphericalCoordinates (core/shell.py) share: coordinates by name and the
+    tensor powers of U, their unitary dim x dim map from coordinate to spin components."""
+
+    def __iter__(self):
+        return iter(self.coords)
+
+    def __getitem__(self, name):
+        return self.coords[self.names.index(name)]
+
+    @classmethod
+    def U_forward(cls, order=1):
+        """coordinate -> spin components of a tensor of the given order"""
+        out = np.array([[1.0 + 0j]])
+        for _ in range(order):
+            out = np.kron(out, cls.U)
+        return out
+
+
 class CartesianCoordinates:
     def __init__(self, *names):
         if len(set(names)) < len(names):

@@ -13,6 +13,7 @@ import numbers
 import numpy as np
 
 from .domain import Domain
+from .mirror import HostMirror, _layout
 
 
 class Operand:
@@ -123,7 +124,9 @@ class Operand:
         return evaluate_expression(self)
 
 
-class Field(Operand):
+class Field(HostMirror, Operand):
+    _grid_hit_sets_scales = True        # (deliberate: the other field kinds leave the scales alone there)
+
     def __init__(self, dist, bases=None, name=None, tensorsig=None, dtype=None):
         if bases is None:
             bases = ()
@@ -142,17 +145,7 @@ class Field(Operand):
                 self.domain.by_axis[ax] is not None for ax in dist.separable_axes):
             from .evaluator import set_pencil_geom
             set_pencil_geom(dist, self.domain.by_axis)
-        self.scales = (1.0,) * dist.dim
-        # device arrays (storage order) and which one is current
-        self._c = None
-        self._g = None
-        self._g_scales = None
-        self.layout = "c"               # layout of the authoritative data
-        # host mirror
-        self._host = None
-        self._host_layout = None
-        self._host_scales = None
-        self._authority = "device"      # 'device' | 'host'
+        self._init_mirror(dist.dim)
         self._adopted = False           # coefficient array is a view into a solver's state vector
         self._tiled = None              # the SystemBuffer whose tile-major rows _c is a view of (SolverBase._enable_state_tiling)
         self._nrows = 0
@@ -175,12 +168,15 @@ class Field(Operand):
     def global_shape(self):
         return self.domain.coeff_shape() if self.layout == "c" else self.domain.grid_shape(self.scales)
 
-    def _remedy_scales(self, scales):
-        if scales is None:
-            return self.scales
-        if isinstance(scales, numbers.Number):
-            return (float(scales),) * self.dist.dim
-        return tuple(float(s) for s in scales)
+    def _global_shape(self, layout, scales):
+        gsp = self.domain.global_coeff_shape() if layout == "c" else self.domain.global_grid_shape(scales)
+        return self.tshape + tuple(gsp)
+
+    def _local_slices(self, layout, scales):
+        return (slice(None),) * len(self.tshape) + self.domain.local_slices(layout, scales)
+
+    def _default_scales(self):
+        return self.scales              # (deliberate: None keeps a Cartesian field's scales; sphere and shell read it as 1)
 
     # ---- host <-> storage order ---------------------------------------------------------------------
     def _to_storage(self, user_arr, layout, scales):
@@ -223,30 +219,32 @@ class Field(Operand):
             self._g_scales = scales
         return self._g
 
-    def _sync_to_device(self):
-        """Upload the host mirror if the user may have touched it."""
-        if self._authority != "host":
-            return
-        self._authority = "device"
-        lay, sc = self._host_layout, self._host_scales
-        st = self._to_storage(self._host, lay, sc)
-        if lay == "c":
+    # ---- hooks of the mirror protocol (core/mirror.py) -------------------------------------------------------------
+    def _host_to_device(self, layout, scales, host):
+        st = self._to_storage(host, layout, scales)
+        if layout == "c":
             self.ex.upload(self._alloc_c(), st)
             self._coeff_written()
         else:
-            self.ex.upload(self._alloc_g(sc), st)
-            self.scales = sc
-        self.layout = lay
+            self.ex.upload(self._alloc_g(scales), st)
+            self.scales = scales
+        self.layout = layout
 
-    def require_coeff_space(self):
-        """Device coefficient array in the NATURAL layout, current (for a state field kept tile-major by its solver: the
-        natural shadow of its rows, refreshed from the state when stale -- read-only for the caller)."""
-        self._sync_to_device()
-        if self.layout == "g":
-            self.dist.transformer.forward(self, self._g, self._g_scales, self._alloc_c())
-            self._coeff_written()
-            self.layout = "c"
-        elif self._c is None:
+    def _device_to_host(self, layout, scales):
+        dev = self.require_coeff_space() if layout == "c" else self.require_grid_space(scales)
+        return self._from_storage(self.ex.download(dev), layout, scales)
+
+    def _forward_transform(self):
+        self.dist.transformer.forward(self, self._g, self._g_scales, self._alloc_c())
+        self._coeff_written()
+
+    def _backward_transform(self, c, scales):
+        self.dist.transformer.backward(self, c, self._alloc_g(scales), scales)      # (deliberate: _g is reused while the scales stay)
+
+    def _coeff_array(self):
+        """NATURAL layout (for a state field kept tile-major by its solver: the natural shadow of its rows, refreshed
+        from the state when stale)."""
+        if self._c is None:
             self._alloc_c()
         if self._tiled is not None:
             return self._tiled.natural_rows(self.ex, self._row0, self._nrows).reshape(self._storage_shape("c", None))
@@ -258,23 +256,9 @@ class Field(Operand):
             return self.require_coeff_space(), 0
         self._sync_to_device()
         if self.layout == "g":
-            self.dist.transformer.forward(self, self._g, self._g_scales, self._alloc_c())
-            self._coeff_written()
+            self._forward_transform()
             self.layout = "c"
         return self._c, int(self._tiled.tiled)
-
-    def require_grid_space(self, scales=None):
-        self._sync_to_device()
-        scales = self._remedy_scales(scales)
-        if self.layout == "g" and self._g_scales == scales:
-            self.scales = scales
-            return self._g
-        c = self.require_coeff_space()
-        g = self._alloc_g(scales)
-        self.dist.transformer.backward(self, c, g, scales)
-        self.layout = "g"
-        self.scales = scales
-        return g
 
     def coeff_data(self):
         """Device coefficient array (storage order), current."""
@@ -289,42 +273,11 @@ class Field(Operand):
         self._authority = "device"
 
     # ---- user access -----------------------------------------------------------------------------
-    def change_scales(self, scales):
-        scales = self._remedy_scales(scales)
-        if scales == self.scales:
-            return
-        self._sync_to_device()
-        if self.layout == "g":
-            self.require_coeff_space()
-        self.scales = scales
-
-    preset_scales = change_scales
-
     def change_layout(self, layout):
         if layout == "c":
             self.require_coeff_space()
         else:
             self.require_grid_space(self.scales)
-
-    def __getitem__(self, key):
-        if isinstance(key, tuple):
-            layout, scales = key
-            self.change_scales(scales)
-        else:
-            layout = key
-        layout = "c" if layout in ("c", "coeff") else "g"
-        if not (self._authority == "host" and self._host_layout == layout
-                and (layout == "c" or self._host_scales == self.scales)):
-            self._sync_to_device()
-            if layout == "c":
-                dev = self.require_coeff_space()
-            else:
-                dev = self.require_grid_space(self.scales)
-            self._host = self._from_storage(self.ex.download(dev), layout, self.scales)
-            self._host_layout, self._host_scales = layout, self.scales
-        # the caller may modify the mirror in place: the host copy is authoritative from now on
-        self._authority = "host"
-        return self._host
 
     def snapshot_async(self, layout):
         """Start copying the current data to the host without blocking the device (executor.download_async); returns a
@@ -333,59 +286,16 @@ class Field(Operand):
         ex = self.ex
         if not hasattr(ex, "download_async") or self._authority == "host":
             return None
-        layout = "c" if layout in ("c", "coeff") else "g"
+        layout = _layout(layout)
         scales = self.scales
         dev = self.require_coeff_space() if layout == "c" else self.require_grid_space(scales)
         pend = ex.download_async(dev)
         return lambda: self._from_storage(pend.wait(), layout, scales)
 
-    def __setitem__(self, key, data):
-        if isinstance(key, tuple):
-            layout, scales = key
-            self.scales = self._remedy_scales(scales)
-        else:
-            layout = key
-        layout = "c" if layout in ("c", "coeff") else "g"
-        shape = self._user_shape(layout, self.scales)
-        if self._host is None or self._host.shape != shape or data is not self._host:
-            host = np.empty(shape)
-            host[...] = data
-            self._host = host
-        self._host_layout, self._host_scales = layout, self.scales
-        self._authority = "host"
-
-    @property
-    def data(self):
-        return self[self.layout if self._authority == "device" else self._host_layout]
-
     def copy(self):
         f = Field(self.dist, bases=self.domain.bases, tensorsig=self.tensorsig, name=self.name)
         f["c"] = self["c"].copy()
         return f
-
-    def fill_random(self, layout=None, scales=None, seed=None, chunk_size=2 ** 20, distribution="standard_normal", **kw):
-        """Reproducible random data: the same global stream the reference draws
-        (core/field.py:898-943, tools/random_arrays.py:7-55: chunks of min(size, chunk_size) from
-        default_rng(seed), C-ordered over (tensor components, global shape))."""
-        if scales is not None:
-            self.change_scales(scales)
-        layout = layout or self.layout
-        layout = "c" if layout in ("c", "coeff") else "g"
-        gsp = self.domain.global_coeff_shape() if layout == "c" else self.domain.global_grid_shape(self.scales)
-        shape = self.tshape + tuple(gsp)
-        n = int(np.prod(shape))
-        cs = min(n, chunk_size)
-        rng = np.random.default_rng(seed)
-        draw = getattr(rng, distribution)
-        out = np.empty(n)
-        pos = 0
-        while pos < n:
-            chunk = draw(size=cs, **kw)
-            m = min(cs, n - pos)
-            out[pos:pos + m] = chunk[:m]
-            pos += m
-        sl = (slice(None),) * len(self.tshape) + self.domain.local_slices(layout, self.scales)
-        self[layout] = out.reshape(shape)[sl]
 
     def low_pass_filter(self, shape=None, scales=None):
         """Zero the modes above the given relative scales by a round trip through a coarser grid

@@ -254,3 +254,45 @@ class IVPLifecycle:
         """core/solvers.py:632-673"""
         from .output import load_state
         return load_state(self, path, index=index, allow_missing=allow_missing)
+
+
+class LUSlotSolver(IVPLifecycle):
+    """What the sphere and the shell initial-value solvers share beyond the life cycle: their construction after the
+    geometry's solver base, the state, the slots `_lus` of the factorizations of a M + b L that the timesteppers ask for
+    (`_lu_params`: the (a, b) of every slot) and the probe of every solve.  Each keeps its own total_modes, Hermitian
+    round trip, the computation of a factorization and its application."""
+
+    def _init_ivp(self, t0, timestepper, enforce_real_cadence, warmup_iterations):
+        """t0: time.time() when the construction began"""
+        from . import timesteppers as ts
+        from .output import OutputEvaluator
+        if isinstance(timestepper, str):
+            timestepper = ts.schemes[timestepper]
+        self.sim_time = self.initial_sim_time = 0.0
+        self._init_lifecycle(enforce_real_cadence, warmup_iterations)
+        self._lus = []
+        self._lu_params = {}
+        self.timestepper = timestepper(self)
+        self.setup_time = time.time() - t0
+        self.evaluator = OutputEvaluator(self)       # analysis handlers: evaluated at the start of a step
+        self._step_hooks = [self.evaluator.step_hook]
+
+    @property
+    def state(self):
+        return self.variables
+
+    def _store_lu(self, inv, a, b, reuse):
+        """keep the factorization of a M + b L in slot `reuse`, or in a new slot; -> its index"""
+        if reuse is not None and reuse >= 0:
+            self._lus[reuse] = inv
+        else:
+            self._lus.append(inv)
+            reuse = len(self._lus) - 1
+        self._lu_params[reuse] = (float(a), float(b))
+        return reuse
+
+    def _probe_solve(self, lu, rhs, x):
+        probe = getattr(self, "solve_probe", None)
+        if probe is not None:                        # parity checks: keep (a, b, rhs, x) of every solve
+            a, b = self._lu_params[lu]
+            probe.append(dict(a=a, b=b, rhs=self.ex.download(rhs).copy(), x=self.ex.download(x).copy()))

@@ -23,19 +23,23 @@ import numpy as np
 from ..tools import sphere as sph
 from . import curvilinear, sphreduce
 from .basis import Jacobi
-from .coords import Coordinate
-from .ivp_common import IVPLifecycle
+from .coords import Coordinate, SpinCoordinates
+from .curviproblem import CurvilinearProblem, NonlinearError
+from .ivp_common import LUSlotSolver
+from .mirror import HostMirror
 from .sphere import S2Coordinates, SphereBasis
 
 
 logger = logging.getLogger(__name__)
 
 
-class SphericalCoordinates:
+class SphericalCoordinates(SpinCoordinates):
     """(azimuth, colatitude, radius); spin and regularity component ordering (-, +, 0)  (core/coords.py:300-390)."""
     dim = 3
     spin_ordering = (-1, +1, 0)
     reg_ordering = (-1, +1, 0)
+    # coordinate (phi, theta, r) -> spin (-, +, 0) components: u[+-] = (u[theta] +- i u[phi]) / sqrt 2, u[0] = u[r]
+    U = np.array([[-1j, 1, 0], [+1j, 1, 0], [0, 0, np.sqrt(2)]]) / np.sqrt(2)
 
     def __init__(self, azimuth, colatitude, radius):
         self.names = (azimuth, colatitude, radius)
@@ -44,21 +48,6 @@ class SphericalCoordinates:
         self.radius = Coordinate(radius, cs=self)
         self.coords = (self.azimuth, self.colatitude, self.radius)
         self.S2coordsys = S2Coordinates(azimuth, colatitude)
-
-    def __iter__(self):
-        return iter(self.coords)
-
-    def __getitem__(self, name):
-        return self.coords[self.names.index(name)]
-
-    @staticmethod
-    def U_forward(order=1):
-        """coordinate (phi, theta, r) -> spin (-, +, 0) components: u[+-] = (u[theta] +- i u[phi]) / sqrt 2, u[0] = u[r]"""
-        U = np.array([[-1j, 1, 0], [+1j, 1, 0], [0, 0, np.sqrt(2)]]) / np.sqrt(2)
-        out = np.array([[1.0 + 0j]])
-        for _ in range(order):
-            out = np.kron(out, U)
-        return out
 
 
 class ShellBasis:
@@ -459,10 +448,6 @@ def forward(dist, basis, rank, g, scales, upto=None):
 # ==================================================================================================
 # ell-dependent radial term lists and operands
 # ==================================================================================================
-
-class NonlinearError(ValueError):
-    pass
-
 
 class EllTermList:
     """Linear map between shell coefficient arrays: out[co][i1][ell][:] = sum A[ell] in[ci][i1][ell][:], matrices
@@ -1492,21 +1477,13 @@ class RadialField(ShOperand):
         return reg @ (P * np.asarray(w, dtype=np.float64)).T
 
 
-class ShellField(ShOperand):
+class ShellField(HostMirror, ShOperand):
     """Tensor field on a ShellBasis (or one of its surfaces): device-resident data with lazily synchronised host mirrors, `['g']` / `['c']`
     in the reference's shapes (packed (m, ell) coefficient layout, core/basis.py:2839-2891)."""
 
     def __init__(self, dist, basis, rank=0, name=None):
         self.dist, self.basis, self.rank, self.name = dist, basis, rank, name
-        self.scales = (1.0, 1.0, 1.0)
-        self._c = None
-        self._g = None
-        self._g_scales = None
-        self.layout = "c"
-        self._host = None
-        self._host_layout = None
-        self._host_scales = None
-        self._authority = "device"
+        self._init_mirror(3)
         self.args = ()
 
     @property
@@ -1550,6 +1527,7 @@ class ShellField(ShOperand):
         return (self.ncomp, 2 * sb.nml, sb.nl, self.basis.Nr)
 
     def _set_device_coeff(self, c):
+        """the solver wrote the coefficients on the device.  Deliberately drops _g, which a sphere field keeps here."""
         self._c = c
         self.layout = "c"
         self._authority = "device"
@@ -1606,99 +1584,37 @@ class ShellField(ShOperand):
         out = out.reshape(self._global_shape("c", self.scales))
         return np.ascontiguousarray(out[self._local_slices("c", self.scales)])
 
-    def _remedy(self, scales):
-        if scales is None:
-            return (1.0,) * 3
-        if isinstance(scales, numbers.Number):
-            return (float(scales),) * 3
-        return tuple(float(s) for s in scales)
-
-    def _sync_to_device(self):
-        if self._authority != "host":
-            return
-        self._authority = "device"
-        lay, sc = self._host_layout, self._host_scales
-        if lay == "c":
-            nat = self._natural_from_packed(self._host)
-            if self._c is None:
-                self._c = self.ex.zeros(self._cshape())
-            self.ex.upload(self._c, nat)
-            self.layout = "c"
+    # ---- hooks of the mirror protocol (core/mirror.py) -------------------------------------------------------------
+    def _host_to_device(self, layout, scales, host):
+        if layout == "c":
+            self.ex.upload(self._coeff_array(), self._natural_from_packed(host))
         else:
-            shape = (self.ncomp,) + self._user_shape("g", sc)[self.rank:]
-            if self._g is None or self._g_scales != sc:
+            shape = (self.ncomp,) + self._user_shape("g", scales)[self.rank:]
+            if self._g is None or self._g_scales != scales:
                 self._g = self.ex.empty(shape)
-                self._g_scales = sc
-            self.ex.upload(self._g, np.ascontiguousarray(self._host.reshape(shape)))
-            self.layout = "g"
-            self.scales = sc
+                self._g_scales = scales
+            self.ex.upload(self._g, np.ascontiguousarray(host.reshape(shape)))
+            self.scales = scales
+        self.layout = layout
 
-    def require_coeff_space(self):
-        self._sync_to_device()
-        if self.layout == "g":
-            self._c = forward(self.dist, self.basis, self.rank, self._g, self._g_scales)
-            self.layout = "c"
+    def _device_to_host(self, layout, scales):
+        shape = self._user_shape(layout, scales)
+        if layout == "c":
+            nat = np.asarray(self.ex.download(self.require_coeff_space()))
+            return self._packed_from_natural(nat).reshape(shape)
+        return np.array(self.ex.download(self.require_grid_space(scales))).reshape(shape)
+
+    def _forward_transform(self):
+        self._c = forward(self.dist, self.basis, self.rank, self._g, self._g_scales)
+
+    def _backward_transform(self, c, scales):
+        self._g = backward(self.dist, self.basis, self.rank, c, scales)       # (deliberate: the transform's own array)
+        self._g_scales = scales
+
+    def _coeff_array(self):
         if self._c is None:
             self._c = self.ex.zeros(self._cshape())
         return self._c
-
-    def require_grid_space(self, scales=None):
-        self._sync_to_device()
-        scales = self._remedy(scales)
-        if self.layout == "g" and self._g_scales == scales:
-            return self._g
-        c = self.require_coeff_space()
-        self._g = backward(self.dist, self.basis, self.rank, c, scales)
-        self._g_scales = scales
-        self.layout = "g"
-        self.scales = scales
-        return self._g
-
-    def change_scales(self, scales):
-        scales = self._remedy(scales)
-        if scales == self.scales:
-            return
-        self._sync_to_device()
-        if self.layout == "g":
-            self.require_coeff_space()
-        self.scales = scales
-
-    preset_scales = change_scales
-
-    def __getitem__(self, key):
-        if isinstance(key, tuple):
-            layout, scales = key
-            self.change_scales(scales)
-        else:
-            layout = key
-        layout = "c" if layout in ("c", "coeff") else "g"
-        if not (self._authority == "host" and self._host_layout == layout
-                and (layout == "c" or self._host_scales == self.scales)):
-            self._sync_to_device()
-            shape = self._user_shape(layout, self.scales)
-            if layout == "c":
-                nat = np.asarray(self.ex.download(self.require_coeff_space()))
-                self._host = self._packed_from_natural(nat).reshape(shape)
-            else:
-                self._host = np.array(self.ex.download(self.require_grid_space(self.scales))).reshape(shape)
-            self._host_layout, self._host_scales = layout, self.scales
-        self._authority = "host"
-        return self._host
-
-    def __setitem__(self, key, data):
-        if isinstance(key, tuple):
-            layout, scales = key
-            self.scales = self._remedy(scales)
-        else:
-            layout = key
-        layout = "c" if layout in ("c", "coeff") else "g"
-        shape = self._user_shape(layout, self.scales)
-        if self._host is None or self._host.shape != shape or data is not self._host:
-            host = np.empty(shape)
-            host[...] = data
-            self._host = host
-        self._host_layout, self._host_scales = layout, self.scales
-        self._authority = "host"
 
     def cfl_frequency_max(self):
         """max over the dealiased grid of the advective CFL frequency of this velocity field (Spherical3DAdvectiveCFL,
@@ -1720,100 +1636,33 @@ class ShellField(ShOperand):
         g = self.eval_g()
         return ex.cfl_max_spherical(g, inv_h, inv_dr)
 
-    def fill_random(self, layout=None, scales=None, seed=None, chunk_size=2 ** 20, distribution="standard_normal", **kw):
-        """The reference's reproducible global random stream (core/field.py:898-943, tools/random_arrays.py:7-55)."""
-        if scales is not None:
-            self.change_scales(scales)
-        layout = "c" if (layout or self.layout) in ("c", "coeff") else "g"
-        shape = self._global_shape(layout, self.scales)
-        n = int(np.prod(shape))
-        cs = min(n, chunk_size)
-        rng = np.random.default_rng(seed)
-        draw = getattr(rng, distribution)
-        out = np.empty(n)
-        pos = 0
-        while pos < n:
-            chunk = draw(size=cs, **kw)
-            m = min(cs, n - pos)
-            out[pos:pos + m] = chunk[:m]
-            pos += m
-        self[layout] = out.reshape(shape)[self._local_slices(layout, self.scales)]
-
 
 # ==================================================================================================
 # problems and solvers (per-ell systems)
 # ==================================================================================================
 
-class ShellProblem:
+class ShellProblem(CurvilinearProblem):
+    operand_type, add_type, scale_type = ShOperand, ShAdd, ShScale
+    operators = dict(lap=lap, grad=grad, div=div, dt=dt, Lift=Lift, lift=Lift, trace=trace, integ=integ,
+                     Laplacian=lap, Gradient=grad, Divergence=div, TimeDerivative=dt, Trace=trace,
+                     Integrate=integ, ave=ave, Average=ave)
+
     def __init__(self, variables, namespace=None, time="t"):
-        self.variables = list(variables)
-        self.dist = self.variables[0].dist
+        super().__init__(variables, namespace, time)
         shells = [v.shell for v in self.variables if hasattr(v, "shell")]
         self.shell = getattr(shells[0], "_root", shells[0])
-        self.equations = []
-        self.namespace = dict(lap=lap, grad=grad, div=div, dt=dt, Lift=Lift, lift=Lift, trace=trace, integ=integ,
-                              Laplacian=lap, Gradient=grad, Divergence=div, TimeDerivative=dt, Trace=trace,
-                              Integrate=integ, ave=ave, Average=ave, np=np, numpy=np)
-        if namespace:
-            self.namespace.update(namespace)
-        for v in self.variables:
-            if v.name:
-                self.namespace[v.name] = v
 
-    def _parse(self, side):
-        if isinstance(side, (ShOperand, numbers.Number)):
-            return side
-        return eval(side, dict(self.namespace))
+    def _lin(self, node):
+        return node.lin(self.variables)
 
-    def add_equation(self, equation, condition=None):
-        from .problems import _split_equation
-        if isinstance(equation, str):
-            lhs_s, rhs_s = _split_equation(equation)
-            lhs, rhs = self._parse(lhs_s), self._parse(rhs_s)
-        else:
-            lhs, rhs = [self._parse(x) for x in equation]
-        if not isinstance(lhs, ShOperand):
-            raise ValueError("LHS must involve the problem variables")
-        if isinstance(rhs, ShOperand) and rhs.has_dt():
-            raise ValueError("time derivatives must be on the LHS")
-        M, L = self._linearize(lhs)
-        if isinstance(rhs, numbers.Number):
-            F = None if rhs == 0 else float(rhs)
-        else:
-            if rhs.rank != lhs.rank:
-                raise ValueError("LHS and RHS tensor signatures differ")
-            F = _converted(rhs, lhs.basis) if isinstance(lhs.basis, ShellBasis) else rhs
-        eq = dict(lhs=lhs, basis=lhs.basis, rank=lhs.rank, ncomp=lhs.ncomp, M=M, L=L, F=F,
-                  string=equation if isinstance(equation, str) else None)
-        self.equations.append(eq)
-        return eq
+    def _numeric_rhs(self, rhs):
+        return None if rhs == 0 else float(rhs)         # (deliberate: the sphere refuses a non-zero number)
 
-    def _linearize(self, lhs):
-        terms = []
+    def _operand_rhs(self, lhs, rhs):
+        return _converted(rhs, lhs.basis) if isinstance(lhs.basis, ShellBasis) else rhs
 
-        def flatten(node, scale):
-            if isinstance(node, ShAdd):
-                for a in node.args:
-                    flatten(a, scale)
-            elif isinstance(node, ShScale):
-                flatten(node.arg, scale * node.a)
-            else:
-                terms.append((scale, node))
-        flatten(lhs, 1.0)
-        M, L = {}, {}
-        for scale, node in terms:
-            try:
-                d, isdt = node.lin(self.variables)
-            except NonlinearError as e:
-                raise ValueError("LHS must be linear in the problem variables: %s" % e)
-            tgt = M if isdt else L
-            for i, tl in d.items():
-                tl = tl.scaled(scale)
-                tgt[i] = tgt[i] + tl if i in tgt else tl
-        return M, L
-
-    def build_solver(self, *args, **kw):
-        return self.solver_class(self, *args, **kw)
+    def _equation_keys(self, lhs):
+        return dict(basis=lhs.basis)
 
 
 class ShellIVP(ShellProblem):
@@ -2068,29 +1917,15 @@ class ShellBoundaryValueSolver(ShellSolverBase):
         self.mark_state_current()
 
 
-class ShellInitialValueSolver(IVPLifecycle, ShellSolverBase):
+class ShellInitialValueSolver(LUSlotSolver, ShellSolverBase):
     """IMEX timestepping of M.dt(X) + L.X = F in a shell with the shared schemes of core/timesteppers.py and the shared
-    life cycle of core/ivp_common.py::IVPLifecycle (stop conditions incl. stop_wall_time, world clocks, evolve)."""
+    life cycle and LU slots of core/ivp_common.py (stop conditions incl. stop_wall_time, world clocks, evolve)."""
 
     def __init__(self, problem, timestepper, enforce_real_cadence=100, warmup_iterations=10, **kw):
         t0 = _time.time()
         ShellSolverBase.__init__(self, problem)
-        from . import timesteppers as ts
-        from .output import OutputEvaluator
-        if isinstance(timestepper, str):
-            timestepper = ts.schemes[timestepper]
-        self.sim_time = self.initial_sim_time = 0.0
-        self._init_lifecycle(enforce_real_cadence, warmup_iterations)
-        self._lus = []
-        self.timestepper = timestepper(self)
-        self.setup_time = _time.time() - t0
-        self.evaluator = OutputEvaluator(self)       # analysis handlers: evaluated at the start of a step
-        self._step_hooks = [self.evaluator.step_hook]
+        self._init_ivp(t0, timestepper, enforce_real_cadence, warmup_iterations)
         self.total_modes = int(self.col_valid.sum()) * 2 * self.nm
-
-    @property
-    def state(self):
-        return self.variables
 
     def _hermitian_round_trip(self, f):
         """the state makes a round trip through the dealiased grid (core/solvers.py:675-681)"""
@@ -2132,6 +1967,7 @@ class ShellInitialValueSolver(IVPLifecycle, ShellSolverBase):
         return self._band
 
     def factor(self, a, b, reuse=-1):
+        # (deliberate: reuse >= 0 alone; the sphere also checks that the slot exists)
         old = self._lus[reuse] if (reuse is not None and reuse >= 0) else None
         band = self._band_setup()
         if band:
@@ -2144,15 +1980,7 @@ class ShellInitialValueSolver(IVPLifecycle, ShellSolverBase):
             inv = dict(index=index, dense=dense)
         else:
             inv = self._inverse_terms(a, b, old=old)
-        if not hasattr(self, "_lu_params"):
-            self._lu_params = {}
-        if reuse is not None and reuse >= 0:
-            self._lus[reuse] = inv
-            self._lu_params[reuse] = (float(a), float(b))
-            return reuse
-        self._lus.append(inv)
-        self._lu_params[len(self._lus) - 1] = (float(a), float(b))
-        return len(self._lus) - 1
+        return self._store_lu(inv, a, b, reuse)
 
     def solve(self, lu, rhs, x):
         inv = self._lus[lu]
@@ -2167,11 +1995,7 @@ class ShellInitialValueSolver(IVPLifecycle, ShellSolverBase):
                     self.ex.dense_group_solve(inv["dense"][k * n2:(k + 1) * n2], rhs.reshape(shape), x.reshape(shape), g)
         else:
             inv.apply(rhs, x)
-        probe = getattr(self, "solve_probe", None)
-        if probe is not None:                        # parity checks: keep (a, b, rhs, x) of every solve
-            a, b = self._lu_params[lu]
-            probe.append(dict(a=a, b=b, rhs=self.ex.download(rhs).copy(), x=self.ex.download(x).copy()))
-
+        self._probe_solve(lu, rhs, x)
 
 
 # ==================================================================================================

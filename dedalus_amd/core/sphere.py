@@ -34,8 +34,10 @@ import numpy as np
 from ..tools import jacobi
 from ..tools import sphere as sph
 from . import sphreduce
-from .coords import Coordinate
-from .ivp_common import IVPLifecycle
+from .coords import Coordinate, SpinCoordinates
+from .curviproblem import CurvilinearProblem, NonlinearError
+from .ivp_common import LUSlotSolver
+from .mirror import HostMirror
 
 
 logger = logging.getLogger(__name__)
@@ -44,31 +46,18 @@ logger = logging.getLogger(__name__)
 # coordinates, basis, distributor
 # ==================================================================================================
 
-class S2Coordinates:
+class S2Coordinates(SpinCoordinates):
     """(azimuth, colatitude); spin component ordering (-, +)  (core/coords.py:201-252)."""
     dim = 2
     spin_ordering = (-1, +1)
+    # unitary map from coordinate (phi, theta) to spin (-, +) components: u[+-] = (u[theta] +- i u[phi]) / sqrt 2
+    U = np.array([[-1j, 1], [+1j, 1]]) / np.sqrt(2)
 
     def __init__(self, azimuth, colatitude):
         self.names = (azimuth, colatitude)
         self.azimuth = Coordinate(azimuth, cs=self)
         self.colatitude = Coordinate(colatitude, cs=self)
         self.coords = (self.azimuth, self.colatitude)
-
-    def __iter__(self):
-        return iter(self.coords)
-
-    def __getitem__(self, name):
-        return self.coords[self.names.index(name)]
-
-    @staticmethod
-    def U_forward(order=1):
-        """Unitary map from coordinate (phi, theta) to spin (-, +) components: u[+-] = (u[theta] +- i u[phi]) / sqrt 2."""
-        U = np.array([[-1j, 1], [+1j, 1]]) / np.sqrt(2)
-        out = np.array([[1.0 + 0j]])
-        for _ in range(order):
-            out = np.kron(out, U)
-        return out
 
 
 class SphereBasis:
@@ -474,10 +463,6 @@ def op_termlist(kind, basis, rank_in, **kw):
 # operands
 # ==================================================================================================
 
-class NonlinearError(ValueError):
-    pass
-
-
 class SOperand:
     """Expression node on the sphere.  rank = tensor rank (components over S2), basis may be None (constant)."""
     __array_priority__ = 100.0
@@ -598,19 +583,12 @@ def _forward(dist, basis, rank, g, scales, upto=None):
     return c
 
 
-class SField(SOperand):
+class SField(HostMirror, SOperand):
     def __init__(self, dist, basis=None, rank=0, name=None):
         self.dist, self.basis, self.rank, self.name = dist, basis, rank, name
-        self.scales = (1.0, 1.0)
-        self._c = None              # device coefficients [ncomp][2 nm][nl] (basis) or host scalar (constant)
-        self._g = None
-        self._g_scales = None
-        self.layout = "c"
-        self._host = None
-        self._host_layout = None
-        self._host_scales = None
-        self._authority = "device"
-        self._const = np.zeros(())   # constants (no basis): their value
+        self._init_mirror(2)         # _c: device coefficients [ncomp][2 nm][nl]; _g: grid data [ncomp][Nphi_g][Ntheta_g]
+        self._const = np.zeros(())   # constants (no basis): their value in grid space, scaled by
+        #                              SphereBasis.constant_mode_value between the layouts; they never leave layout "c"
         self.args = ()
 
     def __repr__(self):
@@ -634,7 +612,12 @@ class SField(SOperand):
         return self._c
 
     def _set_device_coeff(self, c):
-        self._c = c
+        """the solver wrote the coefficients on the device (a constant: its value).  Deliberately keeps _g, which a shell
+        field drops here."""
+        if self.basis is None:
+            self._const = c
+        else:
+            self._c = c
         self.layout = "c"
         self._authority = "device"
 
@@ -646,115 +629,49 @@ class SField(SOperand):
             return t + self.basis.grid_shape(scales)
         return t + self.basis.packed_shape()
 
-    def _remedy(self, scales):
-        if scales is None:
-            return (1.0, 1.0)
-        if isinstance(scales, numbers.Number):
-            return (float(scales),) * 2
-        return tuple(float(s) for s in scales)
-
-    def _sync_to_device(self):
-        if self._authority != "host":
-            return
-        self._authority = "device"
-        lay, sc = self._host_layout, self._host_scales
+    # ---- hooks of the mirror protocol (core/mirror.py) -------------------------------------------------------------
+    def _host_to_device(self, layout, scales, host):
         if self.basis is None:
-            self._const = np.array(self._host).reshape(()) * (1.0 if lay == "g" else SphereBasis.constant_mode_value)
+            self._const = np.array(host).reshape(()) * (1.0 if layout == "g" else SphereBasis.constant_mode_value)
             return
-        if lay == "c":
+        if layout == "c":
             rows, cols, ok = self.basis.pack_index()
             nat = np.zeros(self._cshape())
             for c in range(self.ncomp):
-                nat[c][rows[ok], cols[ok]] = self._host.reshape((self.ncomp,) + rows.shape)[c][ok]
+                nat[c][rows[ok], cols[ok]] = host.reshape((self.ncomp,) + rows.shape)[c][ok]
             self.ex.upload(self._alloc_c(), nat)
-            self.layout = "c"
         else:
-            Np, Nt = self.basis.grid_shape(sc)
-            if self._g is None or self._g_scales != sc:
+            Np, Nt = self.basis.grid_shape(scales)
+            if self._g is None or self._g_scales != scales:
                 self._g = self.ex.empty((self.ncomp, Np, Nt))
-                self._g_scales = sc
-            self.ex.upload(self._g, np.ascontiguousarray(self._host.reshape(self.ncomp, Np, Nt)))
-            self.layout = "g"
-            self.scales = sc
+                self._g_scales = scales
+            self.ex.upload(self._g, np.ascontiguousarray(host.reshape(self.ncomp, Np, Nt)))
+            self.scales = scales
+        self.layout = layout
 
-    def require_coeff_space(self):
-        self._sync_to_device()
+    def _device_to_host(self, layout, scales):
+        shape = self._user_shape(layout, scales)
         if self.basis is None:
-            return None
-        if self.layout == "g":
-            self._c = _forward(self.dist, self.basis, self.rank, self._g, self._g_scales)
-            self.layout = "c"
-        return self._alloc_c()
+            v = float(self._const) * (1.0 if layout == "g" else 1.0 / SphereBasis.constant_mode_value)
+            return np.full(shape, v)
+        if layout == "g":
+            return np.array(self.ex.download(self.require_grid_space(scales))).reshape(shape)
+        nat = np.asarray(self.ex.download(self.require_coeff_space()))
+        rows, cols, ok = self.basis.pack_index()
+        out = np.zeros((self.ncomp,) + rows.shape)
+        for c in range(self.ncomp):
+            out[c][ok] = nat[c][rows[ok], cols[ok]]
+        return out.reshape(shape)
 
-    def require_grid_space(self, scales=None):
-        self._sync_to_device()
-        scales = self._remedy(scales)
-        if self.layout == "g" and self._g_scales == scales:
-            return self._g
-        c = self.require_coeff_space()
-        self._g = _backward(self.dist, self.basis, self.rank, c, scales)
+    def _forward_transform(self):
+        self._c = _forward(self.dist, self.basis, self.rank, self._g, self._g_scales)
+
+    def _backward_transform(self, c, scales):
+        self._g = _backward(self.dist, self.basis, self.rank, c, scales)      # (deliberate: the transform's own array)
         self._g_scales = scales
-        self.layout = "g"
-        self.scales = scales
-        return self._g
 
-    def change_scales(self, scales):
-        scales = self._remedy(scales)
-        if scales == self.scales:
-            return
-        self._sync_to_device()
-        if self.basis is not None and self.layout == "g":
-            self.require_coeff_space()
-        self.scales = scales
-
-    preset_scales = change_scales
-
-    def __getitem__(self, key):
-        if isinstance(key, tuple):
-            layout, scales = key
-            self.change_scales(scales)
-        else:
-            layout = key
-        layout = "c" if layout in ("c", "coeff") else "g"
-        if not (self._authority == "host" and self._host_layout == layout
-                and (layout == "c" or self._host_scales == self.scales)):
-            self._sync_to_device()
-            shape = self._user_shape(layout, self.scales)
-            if self.basis is None:
-                v = float(self._const) * (1.0 if layout == "g" else 1.0 / SphereBasis.constant_mode_value)
-                self._host = np.full(shape, v)
-            elif layout == "c":
-                nat = np.asarray(self.ex.download(self.require_coeff_space()))
-                rows, cols, ok = self.basis.pack_index()
-                out = np.zeros((self.ncomp,) + rows.shape)
-                for c in range(self.ncomp):
-                    out[c][ok] = nat[c][rows[ok], cols[ok]]
-                self._host = out.reshape(shape)
-            else:
-                g = self.require_grid_space(self.scales)
-                self._host = np.array(self.ex.download(g)).reshape(shape)
-            self._host_layout, self._host_scales = layout, self.scales
-        self._authority = "host"
-        return self._host
-
-    def __setitem__(self, key, data):
-        if isinstance(key, tuple):
-            layout, scales = key
-            self.scales = self._remedy(scales)
-        else:
-            layout = key
-        layout = "c" if layout in ("c", "coeff") else "g"
-        shape = self._user_shape(layout, self.scales)
-        if self._host is None or self._host.shape != shape or data is not self._host:
-            host = np.empty(shape)
-            host[...] = data
-            self._host = host
-        self._host_layout, self._host_scales = layout, self.scales
-        self._authority = "host"
-
-    @property
-    def data(self):
-        return self[self.layout if self._authority == "device" else self._host_layout]
+    def _coeff_array(self):
+        return None if self.basis is None else self._alloc_c()         # (a constant has no coefficient array)
 
     # ---- evaluation / linearisation ------------------------------------------------------------------------------
     def eval_c(self):
@@ -1168,83 +1085,25 @@ def dt(a):
 # problems and solvers
 # ==================================================================================================
 
-def _split_equation(eq):
-    from .problems import _split_equation as f
-    return f(eq)
+class SphereProblem(CurvilinearProblem):
+    operand_type, add_type, scale_type = SOperand, SAdd, SScale
+    operators = dict(grad=grad, div=div, lap=lap, skew=skew, MulCosine=MulCosine, ave=ave, dt=dt,
+                     Gradient=grad, Divergence=div, Laplacian=lap, Skew=skew, Average=ave, TimeDerivative=dt)
 
-
-class SphereProblem:
     def __init__(self, variables, namespace=None, time="t"):
-        self.variables = list(variables)
-        self.dist = self.variables[0].dist
+        super().__init__(variables, namespace, time)
         self.basis = _basis_of(*self.variables)
-        self.equations = []
-        self.namespace = dict(grad=grad, div=div, lap=lap, skew=skew, MulCosine=MulCosine, ave=ave, dt=dt,
-                              Gradient=grad, Divergence=div, Laplacian=lap, Skew=skew, Average=ave,
-                              TimeDerivative=dt, np=np, numpy=np)
-        if namespace:
-            self.namespace.update({k: v for k, v in namespace.items()})
-        for v in self.variables:
-            if v.name:
-                self.namespace[v.name] = v
 
-    def _parse(self, side):
-        if isinstance(side, (SOperand, numbers.Number)):
-            return side
-        return eval(side, dict(self.namespace))
+    def _lin(self, node):
+        return node.lin(self.variables, self.basis)
 
-    def add_equation(self, equation, condition=None):
-        if isinstance(equation, str):
-            lhs_s, rhs_s = _split_equation(equation)
-            lhs, rhs = self._parse(lhs_s), self._parse(rhs_s)
-        else:
-            lhs, rhs = [self._parse(s) for s in equation]
-        if not isinstance(lhs, SOperand):
-            raise ValueError("LHS must involve the problem variables")
-        if isinstance(rhs, SOperand) and rhs.has_dt():
-            raise ValueError("time derivatives must be on the LHS")
-        M, L = self._linearize(lhs)
-        if isinstance(rhs, numbers.Number):
-            if rhs != 0:
-                raise NotImplementedError("non-zero constant right-hand sides on the sphere")
-            F = None
-        else:
-            if rhs.rank != lhs.rank:
-                raise ValueError("LHS and RHS tensor signatures differ")
-            F = rhs
-        constant = bool(getattr(lhs, "is_constant", False))
-        eq = dict(lhs=lhs, rank=lhs.rank, ncomp=lhs.ncomp, M=M, L=L, F=F, constant=constant,
-                  string=equation if isinstance(equation, str) else None)
-        self.equations.append(eq)
-        return eq
+    def _numeric_rhs(self, rhs):
+        if rhs != 0:                    # (deliberate: the shell keeps such a number)
+            raise NotImplementedError("non-zero constant right-hand sides on the sphere")
+        return None
 
-    def _linearize(self, lhs):
-        """Split the LHS sum into dt-terms (M) and the rest (L): {variable index: TermList} each."""
-        terms = []
-
-        def flatten(node, scale):
-            if isinstance(node, SAdd):
-                for a in node.args:
-                    flatten(a, scale)
-            elif isinstance(node, SScale):
-                flatten(node.arg, scale * node.a)
-            else:
-                terms.append((scale, node))
-        flatten(lhs, 1.0)
-        M, L = {}, {}
-        for scale, node in terms:
-            try:
-                d, isdt = node.lin(self.variables, self.basis)
-            except NonlinearError as e:
-                raise ValueError("LHS must be linear in the problem variables: %s" % e)
-            tgt = M if isdt else L
-            for i, tl in d.items():
-                tl = tl.scaled(scale)
-                tgt[i] = tgt[i] + tl if i in tgt else tl
-        return M, L
-
-    def build_solver(self, *args, **kw):
-        return self.solver_class(self, *args, **kw)
+    def _equation_keys(self, lhs):
+        return dict(constant=bool(getattr(lhs, "is_constant", False)))
 
 
 class SphereIVP(SphereProblem):
@@ -1508,33 +1367,18 @@ class SphereBoundaryValueSolver(SphereSolverBase):
         for v, c0 in zip(self.variables, self.col0):
             if v.basis is None:
                 val = np.asarray(self.ex.download(self.X[c0:c0 + 1]))[0, 0, 0]
-                v._const = np.array(val * SphereBasis.constant_mode_value)
-                v._authority = "device"
+                v._set_device_coeff(np.array(val * SphereBasis.constant_mode_value))
 
 
-class SphereInitialValueSolver(IVPLifecycle, SphereSolverBase):
+class SphereInitialValueSolver(LUSlotSolver, SphereSolverBase):
     """IMEX timestepping of M.dt(X) + L.X = F on the sphere (core/solvers.py:InitialValueSolver); the schemes are
-    the shared ones of core/timesteppers.py, the life cycle is the shared core/ivp_common.py::IVPLifecycle."""
+    the shared ones of core/timesteppers.py, the life cycle and the LU slots the shared ones of core/ivp_common.py."""
 
     def __init__(self, problem, timestepper, enforce_real_cadence=100, warmup_iterations=10, **kw):
         t0 = _time.time()
         SphereSolverBase.__init__(self, problem)
-        from . import timesteppers as ts
-        if isinstance(timestepper, str):
-            timestepper = ts.schemes[timestepper]
-        self.sim_time = self.initial_sim_time = 0.0
-        self._init_lifecycle(enforce_real_cadence, warmup_iterations)
-        self._lus = []
-        self.timestepper = timestepper(self)
-        self.setup_time = _time.time() - t0
+        self._init_ivp(t0, timestepper, enforce_real_cadence, warmup_iterations)
         self.total_modes = int(self.col_valid.sum()) * 2
-        from .output import OutputEvaluator
-        self.evaluator = OutputEvaluator(self)       # analysis handlers: evaluated at the start of a step
-        self._step_hooks = [self.evaluator.step_hook]
-
-    @property
-    def state(self):
-        return self.variables
 
     def _hermitian_round_trip(self, f):
         if isinstance(f, SField) and f.basis is not None:
@@ -1543,22 +1387,10 @@ class SphereInitialValueSolver(IVPLifecycle, SphereSolverBase):
 
     # interface used by the shared timesteppers ------------------------------------------------------------------
     def factor(self, a, b, reuse=-1):
+        # (deliberate: the slot is looked up only when it exists; the shell checks reuse >= 0 alone)
         prev = self._lus[reuse] if (reuse is not None and 0 <= reuse < len(self._lus)) else None
-        inv = self._inverse_batch(a, b, old=prev)
-        if not hasattr(self, "_lu_params"):
-            self._lu_params = {}
-        if reuse is not None and reuse >= 0:
-            self._lus[reuse] = inv
-            self._lu_params[reuse] = (float(a), float(b))
-            return reuse
-        self._lus.append(inv)
-        self._lu_params[len(self._lus) - 1] = (float(a), float(b))
-        return len(self._lus) - 1
+        return self._store_lu(self._inverse_batch(a, b, old=prev), a, b, reuse)
 
     def solve(self, lu, rhs, x):
         self._lus[lu].apply(rhs, x)
-        probe = getattr(self, "solve_probe", None)
-        if probe is not None:                        # parity checks: keep (a, b, rhs, x) of every solve
-            a, b = self._lu_params[lu]
-            probe.append(dict(a=a, b=b, rhs=self.ex.download(rhs).copy(), x=self.ex.download(x).copy()))
-
+        self._probe_solve(lu, rhs, x)
