@@ -91,6 +91,18 @@ class ShellBasis:
             self._plans[key] = RadialBasis(self)
         return self._plans[key]
 
+    @property
+    def meridional_basis(self):
+        """Tag for axisymmetric fields (the reference's clone with one azimuthal point, core/basis.py:4470-4472), which
+        rotating-shell scripts use for the rotation axis: ez['g'][1] = -sin(theta), ez['g'][2] = cos(theta).  A field
+        built on it is STORED ON THE FULL SHELL BASIS (its grid data has the full azimuthal size, and values assigned
+        from (1, Ntheta, Nr) arrays broadcast along phi); it can be used wherever a shell field can, in particular as
+        a factor of cross()."""
+        key = ("meridional",)
+        if key not in self._plans:
+            self._plans[key] = MeridionalBasis(self)
+        return self._plans[key]
+
     def S2_basis(self, radius=1):
         key = ("surf", float(radius))
         if key not in self._plans:
@@ -258,6 +270,8 @@ class ShellDistributor:
             return ConstField(self, name=name)
         if isinstance(bases, RadialBasis):
             return RadialField(self, bases.shell, rank=rank, name=name)
+        if isinstance(bases, MeridionalBasis):
+            bases = bases.shell
         if not isinstance(bases, (ShellBasis, SurfaceBasis)):
             raise NotImplementedError("fields in spherical coordinates need a ShellBasis, one of its surfaces or its radial basis")
         return ShellField(self, bases, rank=rank, name=name)
@@ -283,6 +297,14 @@ class ShellDistributor:
 
 
 class RadialBasis:
+    def __init__(self, shell):
+        self.shell = shell
+        self.k = shell.k
+
+
+class MeridionalBasis:
+    """ShellBasis.meridional_basis: fields built on it live on the full shell basis `shell`."""
+
     def __init__(self, shell):
         self.shell = shell
         self.k = shell.k
@@ -451,11 +473,20 @@ def forward(dist, basis, rank, g, scales, upto=None):
 
 class EllTermList:
     """Linear map between shell coefficient arrays: out[co][i1][ell][:] = sum A[ell] in[ci][i1][ell][:], matrices
-    stored as [nl][Nr][Nr] (sphere-surface operands use the leading 1 x Nr / Nr x 1 / 1 x 1 block)."""
+    stored as [nl][Nr][Nr] (sphere-surface operands use the leading 1 x Nr / Nr x 1 / 1 x 1 block).
+    rot (optional, one 0 / 1 per term): a term with rot = 1 is i A on the complex number cos + i msin of every azimuthal
+    mode, i.e. out[2m] += -A in[2m + 1], out[2m + 1] += +A in[2m] (the curl); i . i = -1 when two
+    such terms are composed."""
 
-    def __init__(self, nco, nci, terms=None):
+    def __init__(self, nco, nci, terms=None, rot=None):
         self.nco, self.nci = nco, nci
         self.terms = list(terms or [])          # (co, ci, mats [nl][Nr][Nr])
+        self.rot = [int(r) for r in rot] if rot is not None else [0] * len(self.terms)
+        assert len(self.rot) == len(self.terms)
+
+    @property
+    def rotated(self):
+        return any(self.rot)
 
     @staticmethod
     def identity(nc, nl, Nr, nr):
@@ -464,29 +495,31 @@ class EllTermList:
         return EllTermList(nc, nc, [(c, c, m.copy()) for c in range(nc)])
 
     def scaled(self, a):
-        return EllTermList(self.nco, self.nci, [(co, ci, a * m) for (co, ci, m) in self.terms])
+        return EllTermList(self.nco, self.nci, [(co, ci, a * m) for (co, ci, m) in self.terms], self.rot)
 
     def __add__(self, other):
         assert (self.nco, self.nci) == (other.nco, other.nci)
-        return EllTermList(self.nco, self.nci, self.terms + other.terms).merged()
+        return EllTermList(self.nco, self.nci, self.terms + other.terms, self.rot + other.rot).merged()
 
     def merged(self):
         acc = {}
-        for (co, ci, m) in self.terms:
-            acc[(co, ci)] = acc[(co, ci)] + m if (co, ci) in acc else np.array(m, dtype=np.float64)
-        return EllTermList(self.nco, self.nci, [(co, ci, m) for (co, ci), m in sorted(acc.items()) if np.any(m != 0)])
+        for (co, ci, m), r in zip(self.terms, self.rot):
+            acc[(co, ci, r)] = acc[(co, ci, r)] + m if (co, ci, r) in acc else np.array(m, dtype=np.float64)
+        keep = [(key, m) for key, m in sorted(acc.items()) if np.any(m != 0)]
+        return EllTermList(self.nco, self.nci, [(co, ci, m) for (co, ci, r), m in keep], [r for (co, ci, r), m in keep])
 
     def compose(self, inner):
         assert self.nci == inner.nco
-        out = []
-        for (co, cm, A) in self.terms:
-            for (cm2, ci, B) in inner.terms:
+        out, rot = [], []
+        for (co, cm, A), ra in zip(self.terms, self.rot):
+            for (cm2, ci, B), rb in zip(inner.terms, inner.rot):
                 if cm2 == cm:
-                    out.append((co, ci, np.matmul(A, B)))
-        return EllTermList(self.nco, inner.nci, out).merged()
+                    out.append((co, ci, -np.matmul(A, B) if (ra and rb) else np.matmul(A, B)))
+                    rot.append(ra ^ rb)
+        return EllTermList(self.nco, inner.nci, out, rot).merged()
 
     def embed(self, row0, col0, nrows, ncols):
-        return EllTermList(nrows, ncols, [(co + row0, ci + col0, m) for (co, ci, m) in self.terms])
+        return EllTermList(nrows, ncols, [(co + row0, ci + col0, m) for (co, ci, m) in self.terms], self.rot)
 
 
 REG = (-1, +1, 0)
@@ -517,7 +550,7 @@ def spin_allowed(ell, idx):
 
 def shell_op_termlist(kind, shell, rank_in, k, **kw):
     """Term list of one operator of the reference's SphericalEllOperator family acting on a rank-`rank_in` tensor
-    in the k-th shell basis: lap (core/operators.py:4109-4152), grad (:3240-3288), div (:3546-3600), convert
+    in the k-th shell basis: lap (core/operators.py:4109-4152), grad (:3240-3288), div (:3546-3600), curl (:3838-3901), convert
     (ConvertSpherical3D, core/basis.py:4822-4842), lift (LiftShell :5155-5199), interp (ShellRadialInterpolate
     :5823-5889)."""
     from ..tools import shellops as so
@@ -570,6 +603,19 @@ def shell_op_termlist(kind, shell, rank_in, k, **kw):
                 fn = lambda ell: so.xi(+1, ell + rt - 1) * so.operator_matrix("D-", ell, rt, Nr, k, radii, alpha)
             terms.append((co, ci, stack(fn, lambda ell: regularity_allowed(ell, t), lambda ell: regularity_allowed(ell, to))))
         return EllTermList(len(idx_out), len(idx_in), terms)
+    if kind == "curl":
+        # SphericalCurl (core/operators.py:3838-3901): purely imaginary radial matrices between the regularity components
+        # (-, +) <-> 0 -- stored as the real factor with rot = 1.  The sign of the factor and the blocks are those of
+        # _radial_matrix (:3889-3901); regindex_out (:3870-3877).
+        if rank_in != 1:
+            raise NotImplementedError("curl of a rank-%d tensor" % rank_in)
+        blocks = ((0, 2, -1.0, +1, +1, "D+"), (1, 2, +1.0, -1, -1, "D-"),       # (in, out, sign, xi mu, xi shift, D)
+                  (2, 0, -1.0, +1, 0, "D-"), (2, 1, +1.0, -1, 0, "D+"))
+        for (ci, co, sign, mu, shift, name) in blocks:
+            rt = REG[ci]
+            terms.append((co, ci, stack(lambda ell: sign * so.xi(mu, ell + rt + shift) * so.operator_matrix(name, ell, rt, Nr, k, radii, alpha),
+                                        lambda ell: regularity_allowed(ell, (ci,)), lambda ell: regularity_allowed(ell, (co,)))))
+        return EllTermList(3, 3, terms, [1] * len(terms)).merged()
     if kind == "trace":              # SphericalTrace (core/operators.py:1783-1826): Q_out^T trace_spin Q_in, identity in n
         if rank_in != 2:
             raise NotImplementedError("trace of a rank-%d tensor" % rank_in)
@@ -743,6 +789,10 @@ class ShOperand:
     def grid_native(self):
         """Grid data when the operand is formed in grid space (products), else None."""
         return None
+
+    def is_grid_native(self):
+        """True when grid_native() gives data (asked before evaluating anything)"""
+        return False
 
     def evaluate(self):
         f = ShellField(self.dist, self.basis, rank=self.rank)
@@ -965,6 +1015,9 @@ class ShUnary(ShOperand):
         ex.grid_map(out, g, Evaluator._map_op(self.func))
         return out
 
+    def is_grid_native(self):
+        return True
+
     def eval_g(self):
         return self.grid_native()
 
@@ -979,6 +1032,9 @@ class ShScale(ShOperand):
     def __init__(self, a, arg):
         self.a, self.arg, self.args = float(a), arg, (arg,)
         self.dist, self.basis, self.rank = arg.dist, arg.basis, arg.rank
+
+    def is_grid_native(self):
+        return self.arg.is_grid_native()
 
     def grid_native(self):
         g = self.arg.grid_native()
@@ -1039,12 +1095,32 @@ class ShAdd(ShOperand):
         self.basis = _common_basis(a, b)
         self.args = (_converted(a, self.basis), _converted(b, self.basis))
 
+    def is_grid_native(self):
+        return isinstance(self.basis, ShellBasis) and all(x.is_grid_native() for x in self.args)
+
+    def grid_native(self):
+        """AddFields.operate adds in the layout its arguments share (core/arithmetic.py:226-251): two operands formed on the
+        grid (products, e.g. - u@grad(u) - cross(ez, u)/Ekman) are added THERE, and the sum is transformed once, in the
+        basis it ends up in."""
+        if not self.is_grid_native():
+            return None
+        ex = self.dist.executor
+        gs = [x.grid_native() for x in self.args]
+        out = ex.empty(tuple(gs[0].shape))
+        ex.lincomb(out, gs, [1.0, 1.0])
+        return out
+
     def eval_c(self):
         ex = self.dist.executor
+        if self.is_grid_native():
+            return forward(self.dist, self.basis, self.rank, self.grid_native(), self.basis.dealias)
         cs = [x.eval_c() for x in self.args]
         out = ex.empty(tuple(cs[0].shape))
         ex.lincomb(out, cs, [1.0, 1.0])
         return out
+
+    def eval_g(self):
+        return self.grid_native() if self.is_grid_native() else _eval_grid(self)
 
     def lin(self, variables):
         out, anydt = {}, None
@@ -1060,7 +1136,7 @@ class ShAdd(ShOperand):
 
 
 class ShLinear(ShOperand):
-    """lap / grad / div / convert / lift / interp of an operand."""
+    """lap / grad / div / curl / convert / lift / interp of an operand."""
 
     def __init__(self, kind, arg, **kw):
         if not isinstance(arg, ShOperand):
@@ -1068,7 +1144,14 @@ class ShLinear(ShOperand):
         self.kind, self.arg, self.args, self.kw = kind, arg, (arg,), kw
         self.dist = arg.dist
         ab = arg.basis
-        if kind in ("lap", "grad", "div", "convert", "interp", "trace", "integ") and not isinstance(ab, ShellBasis):
+        if kind == "curl":
+            if isinstance(arg, RadialField):
+                raise NotImplementedError("curl of a radial operand")
+            if isinstance(ab, SurfaceBasis):
+                raise NotImplementedError("curl of a surface operand")
+            if arg.rank != 1:
+                raise NotImplementedError("curl of a scalar" if arg.rank == 0 else "curl of a rank-%d tensor" % arg.rank)
+        if kind in ("lap", "grad", "div", "curl", "convert", "interp", "trace", "integ") and not isinstance(ab, ShellBasis):
             raise NotImplementedError("%s of an operand without a shell basis" % kind)
         if kind == "lap":
             self.basis, self.rank = ab.derivative_basis(2), arg.rank
@@ -1078,6 +1161,8 @@ class ShLinear(ShOperand):
             if arg.rank < 1:
                 raise ValueError("div needs a tensor of rank >= 1")
             self.basis, self.rank = ab.derivative_basis(1), arg.rank - 1
+        elif kind == "curl":
+            self.basis, self.rank = ab.derivative_basis(1), 1
         elif kind == "convert":
             self.basis, self.rank = ab.derivative_basis(kw["dk"]), arg.rank
         elif kind == "interp":
@@ -1127,15 +1212,28 @@ class ShLinear(ShOperand):
             tl = self.termlist()
             seqs, slot_map = operate_slot_sequences(sb)
             terms = [(co, ci, np.concatenate([m] + [sum(m[l] for l in seq)[None] for seq in seqs])) for (co, ci, m) in tl.terms]
-            slot_map = np.ascontiguousarray(slot_map[2 * sb.m0:2 * (sb.m0 + sb.nml)])
-            self._dev = (ex, ex.make_ell_terms(sb.nml, sb.nl, shell.Nr, tl.nco, terms, slot_map))
+            slot_map = np.array(slot_map[2 * sb.m0:2 * (sb.m0 + sb.nml)])       # a copy: the cached map is shared by all operators
+            if tl.rotated:
+                # the msin part of (m, ell) = (0, 0) is no mode of a vector (valid_elements, core/basis.py:4299-4305): the
+                # rotation must not carry it into the cos part
+                if sb.m0 == 0:
+                    slot_map[1, 0] = -1
+                self._dev = (ex, ex.make_ell_terms(sb.nml, sb.nl, shell.Nr, tl.nco, terms, slot_map, rot=tl.rot))
+            else:
+                self._dev = (ex, ex.make_ell_terms(sb.nml, sb.nl, shell.Nr, tl.nco, terms, slot_map))
         x = _padded(ex, self.arg.eval_c(), shell.Nr)
         y = ex.empty((self.ncomp, 2 * sb.nml, sb.nl, shell.Nr))
         self._dev[1].apply(x, y)
         return _unpadded(ex, y, self.basis.Nr if self.basis is not None else 1)
 
+    def is_grid_native(self):
+        return self.kind == "convert" and self.arg.is_grid_native()
+
+    def grid_native(self):
+        return self.arg.grid_native() if self.kind == "convert" else None      # Convert.operate copies grid data
+
     def eval_g(self):
-        return _eval_grid(self)
+        return self.grid_native() if self.is_grid_native() else _eval_grid(self)
 
     def lin(self, variables):
         d, dt = self.arg.lin(variables)
@@ -1184,16 +1282,19 @@ def _eval_grid(x):
 
 
 class ShProduct(ShOperand):
-    """a * b (tensor product) or a @ b (contraction of the last index of a with the first of b).  With a radial NCC
+    """a * b (tensor product), a @ b (contraction of the last index of a with the first of b) or cross(a, b) of two
+    vectors (CrossProduct, core/arithmetic.py:678-742; grid evaluation only).  With a radial NCC
     (RadialField) as one factor the product is linear in the other one (LHS terms: rvec*lift(tau), b*er); otherwise
     it is evaluated on the dealiased grid (MultiplyFields / DotProduct, core/arithmetic.py:586-674)."""
 
-    def __init__(self, a, b, contract=False):
-        self.args, self.contract = (a, b), contract
+    def __init__(self, a, b, contract=False, cross=False):
+        self.args, self.contract, self.cross = (a, b), contract, cross
         self.dist = a.dist
         if contract and (a.rank < 1 or b.rank < 1):
             raise ValueError("dot product needs tensors of rank >= 1")
-        self.rank = a.rank + b.rank - (2 if contract else 0)
+        if cross and (a.rank != 1 or b.rank != 1):
+            raise NotImplementedError("cross product of operands that are not both vectors")
+        self.rank = 1 if cross else a.rank + b.rank - (2 if contract else 0)
         ncc = [x for x in (a, b) if isinstance(x, RadialField)]
         other = [x for x in (a, b) if not isinstance(x, RadialField)]
         if len(ncc) == 1:
@@ -1213,10 +1314,13 @@ class ShProduct(ShOperand):
         Nt = self.dist.theta_range(Nt)[1]
         ga = a.grid_broadcast(ex, self.basis, (Np, Nt, Ng)) if isinstance(a, RadialField) else a.eval_g()
         gb = b.grid_broadcast(ex, self.basis, (Np, Nt, Ng)) if isinstance(b, RadialField) else b.eval_g()
-        terms, nout = _bilinear_terms3(a.rank, b.rank, self.contract)
+        terms, nout = (CROSS_TERMS, 3) if self.cross else _bilinear_terms3(a.rank, b.rank, self.contract)
         out = ex.empty((nout, Np, Nt, Ng))
         ex.bilinear(out, nout, ga, gb, Np * Nt * Ng, terms)
         return out
+
+    def is_grid_native(self):
+        return True
 
     def eval_c(self):
         return forward(self.dist, self.basis, self.rank, self.grid_native(), self.basis.dealias)
@@ -1232,11 +1336,18 @@ class ShProduct(ShOperand):
             ncc, arg, ncc_first = b, a, False
         else:
             raise NonlinearError("products of fields are nonlinear")
+        if self.cross:
+            raise NotImplementedError("cross product with a radial field in a shell LHS")
         if not isinstance(arg.basis, ShellBasis):
             raise NotImplementedError("NCC product with an operand that has no shell basis")
         d, isdt = arg.lin(variables)
         tl = ncc_termlist(ncc, arg.basis, arg.rank, ncc_first, self.contract)
         return {i: tl.compose(t) for i, t in d.items()}, isdt
+
+
+# a x b in the component order (phi, theta, r), which is LEFT-handed (SphericalCoordinates.right_handed = False,
+# core/coords.py:326): CrossProduct.operate_left_handed (core/arithmetic.py:719-728), as (out, ia, ib, sign)
+CROSS_TERMS = [(0, 2, 1, 1.0), (0, 1, 2, -1.0), (1, 0, 2, 1.0), (1, 2, 0, -1.0), (2, 1, 0, 1.0), (2, 0, 1, -1.0)]
 
 
 def _bilinear_terms3(rank_a, rank_b, contract):
@@ -1349,6 +1460,23 @@ def grad(a):
 
 def div(a):
     return ShLinear("div", a)
+
+
+def curl(a):
+    """curl of a vector operand on a ShellBasis; the result lives in the k + 1 basis (SphericalCurl._output_basis)"""
+    if not isinstance(a, ShOperand):
+        raise ValueError("curl needs a field operand")
+    return ShLinear("curl", a)
+
+
+def cross(a, b):
+    """a x b of two vector operands, formed on the dealiased grid; a RadialField factor is broadcast to the grid"""
+    if not (isinstance(a, ShOperand) and isinstance(b, ShOperand)):
+        raise ValueError("cross needs two field operands")
+    return ShProduct(a, b, cross=True)
+
+
+Curl, CrossProduct = curl, cross
 
 
 def dt(a):
@@ -1645,7 +1773,7 @@ class ShellProblem(CurvilinearProblem):
     operand_type, add_type, scale_type = ShOperand, ShAdd, ShScale
     operators = dict(lap=lap, grad=grad, div=div, dt=dt, Lift=Lift, lift=Lift, trace=trace, integ=integ,
                      Laplacian=lap, Gradient=grad, Divergence=div, TimeDerivative=dt, Trace=trace,
-                     Integrate=integ, ave=ave, Average=ave)
+                     Integrate=integ, ave=ave, Average=ave, curl=curl, Curl=curl, cross=cross, CrossProduct=cross)
 
     def __init__(self, variables, namespace=None, time="t"):
         super().__init__(variables, namespace, time)
@@ -1653,7 +1781,10 @@ class ShellProblem(CurvilinearProblem):
         self.shell = getattr(shells[0], "_root", shells[0])
 
     def _lin(self, node):
-        return node.lin(self.variables)
+        d, isdt = node.lin(self.variables)
+        if any(t.rotated for t in d.values()):
+            raise NotImplementedError("curl in a shell LHS: per-ell systems are real")
+        return d, isdt
 
     def _numeric_rhs(self, rhs):
         return None if rhs == 0 else float(rhs)         # (deliberate: the sphere refuses a non-zero number)

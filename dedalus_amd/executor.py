@@ -473,9 +473,12 @@ class HipExecutor:
         """terms: list of (co, ci, d, coef complex [nm][nl]) -> device term list (ddh_sphere_terms_create)."""
         return SphereTerms(self, nm, nl, ncomp_out, terms)
 
-    def make_ell_terms(self, nm, nl, nr, ncomp_out, terms, slot_map=None):
+    def make_ell_terms(self, nm, nl, nr, ncomp_out, terms, slot_map=None, rot=None):
         """terms: list of (co, ci, mats [nmat][nr][nr]); slot_map [2 nm][nl] -> matrix index or -1 (default: ell where
-        ell >= m) -> device radial operator (ddh_ell_terms_create)."""
+        ell >= m) -> device radial operator (ddh_ell_terms_create).  rot: per term 0 / 1; a term with rot = 1 is i times
+        its matrix on cos + i msin (ddh_ell_terms_create_cx: the curl)."""
+        if rot is not None and any(rot):
+            return EllTermsCx(self, nm, nl, nr, ncomp_out, terms, slot_map, rot)
         return EllTerms(self, nm, nl, nr, ncomp_out, terms, slot_map)
 
     def make_cgemv_batch(self, nm, nl, ncomp, mats):
@@ -821,6 +824,52 @@ class BorderedBandInverse:
         libhip.call("ddh_ellband_bordered_inverse", ptr(self.x), self.n, self.j0, ptr(self.wM), ptr(self.wL), self.dM, self.dL,
                     float(a), float(b), ptr(self.out), self.ex.dev.stream)
         return self.out
+
+
+class EllTermsCx:
+    """Device term list with rotated (imaginary) terms: one streaming launch for the real and the rotated terms."""
+
+    def __init__(self, ex, nm, nl, nr, ncomp_out, terms, slot_map, rot):
+        self.ex = ex
+        if len(rot) != len(terms):
+            raise ValueError("one rot flag per term")
+        order = sorted(range(len(terms)), key=lambda i: terms[i][0])
+        terms, rot = [terms[i] for i in order], [int(rot[i]) for i in order]
+        co = np.ascontiguousarray([t[0] for t in terms], dtype=np.int32)
+        ci = np.ascontiguousarray([t[1] for t in terms], dtype=np.int32)
+        rt = np.ascontiguousarray(rot, dtype=np.int32)
+        nmat = int(terms[0][2].shape[0])
+        mats = np.zeros((len(terms), nmat, nr, nr))
+        for i, t in enumerate(terms):
+            mats[i] = t[2]
+        sm = np.ascontiguousarray(default_slot_map(nm, nl) if slot_map is None else slot_map, dtype=np.int32)
+        if sm.shape != (2 * nm, nl):
+            raise ValueError("slot map must be [2 nm][nl]")
+        self.shape_in = (int(ci.max()) + 1, 2 * nm, nl, nr)
+        self.shape_out = (ncomp_out, 2 * nm, nl, nr)
+        self.handle = C.c_uint64(0)
+        libhip.call("ddh_ell_terms_create_cx", C.byref(self.handle), int(nm), int(nl), int(nr), int(ncomp_out),
+                    self.shape_in[0], len(terms), libhip.as_ip(co), libhip.as_ip(ci), libhip.as_ip(rt), nmat,
+                    libhip.as_dp(mats), libhip.as_ip(sm))
+        uses = np.bincount(sm[sm >= 0].ravel(), minlength=nmat)[:nmat]
+        nnz = np.count_nonzero(mats.reshape(mats.shape[0], nmat, -1), axis=2).sum(axis=0)
+        self._madds = float(np.dot(nnz, uses))
+        self._mat_bytes = float(np.count_nonzero(mats)) * 8
+
+    def apply(self, x, y):
+        if tuple(x.shape)[1:] != self.shape_in[1:] or int(x.shape[0]) < self.shape_in[0] or tuple(y.shape) != self.shape_out:
+            raise ValueError("ell terms: operand shapes %s -> %s do not match the term list (%s -> %s)"
+                             % (tuple(x.shape), tuple(y.shape), self.shape_in, self.shape_out))
+        if not (x.is_contiguous() and y.is_contiguous()):
+            raise ValueError("ell terms: contiguous operands only")
+        libhip.note_cost("ddh_ell_terms_apply_cx", 2.0 * self._madds, self._mat_bytes + (x.numel() + y.numel()) * 8)
+        libhip.call("ddh_ell_terms_apply_cx", self.handle, ptr(x), ptr(y), self.ex.dev.stream)
+
+    def __del__(self):
+        try:
+            libhip.call("ddh_destroy", self.handle)
+        except Exception:
+            pass
 
 
 class DenseEllTerms:

@@ -46,9 +46,11 @@ def _dispatch(name, cart):
     return f
 
 
-grad, div, lap, skew, ave, dt, trace, integ = (_dispatch(n, c) for n, c in (
+grad, div, lap, skew, ave, dt, trace, integ, curl, cross = (_dispatch(n, c) for n, c in (
     ("grad", grad), ("div", div), ("lap", lap), ("skew", skew), ("ave", ave), ("dt", dt), ("trace", trace),
-    ("integ", integ)))
+    ("integ", integ), ("curl", curl), ("cross", cross)))
+Curl = curl
+CrossProduct = _dispatch("cross", CrossProduct)
 Average = _dispatch("ave", Average)          # Average(f, coords['phi']) of sphere / shell operands; else the Cartesian class
 MulCosine = _sphere.MulCosine
 _CartesianIVP, _CartesianLBVP = IVP, LBVP

@@ -222,6 +222,18 @@ int ddh_ell_terms_apply(ddh_handle h, const double *x, double *y, void *stream);
 /* accumulate != 0: y += A x (dense term lists only: the FP64 MFMA per-ell GEMM path); used to apply a term list
  * split into its banded part (first, writes y) and its dense blocks (second, accumulates).              */
 int ddh_ell_terms_apply_acc(ddh_handle h, const double *x, double *y, int accumulate, void *stream);
+/* Term lists with imaginary terms (the curl of shell vector fields): as ddh_ell_terms_create, plus a flag per term.
+ * rot_h[t] = 0: the term acts as above.  rot_h[t] = 1: the term is i A_t on the complex number cos + i msin of every
+ * azimuthal mode, y[co][2m + 0] += -A x[ci][2m + 1], y[co][2m + 1] += +A x[ci][2m + 0] -- the real-dtype branch of
+ * SphericalCurl.operate (core/operators.py:3944-3978) with the purely imaginary radial matrices of
+ * SphericalCurl._radial_matrix (:3889-3901); the same rotation as mult_1j in its subproblem_matrix (:3929).  A slot
+ * with slot_map_h < 0 is never read (not as the other part of its pair either) and receives +0.  Real and rotated
+ * terms of an output component are summed in one launch, in term order, without atomics; banded matrices are
+ * streamed (no GEMM path).  ncomp_in: components of x.  ncomp_in * nr * 64 bytes of LDS must fit 160 KiB.         */
+int ddh_ell_terms_create_cx(ddh_handle *h, int nm, int nl, int nr, int ncomp_out, int ncomp_in, int nterms,
+                            const int *co_h, const int *ci_h, const int *rot_h, int nmat, const double *mats_h,
+                            const int *slot_map_h);
+int ddh_ell_terms_apply_cx(ddh_handle h, const double *x, double *y, void *stream);
 
 /* ---- device factorization of the curvilinear subproblems (SURVEY 8a row a9 for configs S and H) ------------------
  * (a M + b L)^-1 for a batch of small dense systems (n <= 1024), real or complex, formed and inverted ON THE DEVICE
