@@ -510,6 +510,10 @@ class EllTermList:
 
     def compose(self, inner):
         assert self.nci == inner.nco
+        if isinstance(inner, EllMixList):                  # matrix-list o mix: the columns of A[ell] scaled by q[ell]
+            out = [(co, ci, A * q[:, None, None]) for (co, cm, A) in self.terms for (cm2, ci, q) in inner.terms if cm2 == cm]
+            rot = [ra for (co, cm, A), ra in zip(self.terms, self.rot) for (cm2, ci, q) in inner.terms if cm2 == cm]
+            return EllTermList(self.nco, inner.nci, out, rot).merged()
         out, rot = [], []
         for (co, cm, A), ra in zip(self.terms, self.rot):
             for (cm2, ci, B), rb in zip(inner.terms, inner.rot):
@@ -520,6 +524,63 @@ class EllTermList:
 
     def embed(self, row0, col0, nrows, ncols):
         return EllTermList(nrows, ncols, [(co + row0, ci + col0, m) for (co, ci, m) in self.terms], self.rot)
+
+
+class EllMixList:
+    """Linear map between shell coefficient arrays that is the identity along n: out[co][i1][ell][:] = sum q[ell] in[ci][i1][ell][:],
+    one real scalar per term and ell (transpose, radial and angular components: DESIGN.md section 9).  Composes with itself
+    and, in both orders, with EllTermList, where it scales the radial matrices per ell."""
+
+    def __init__(self, nco, nci, terms=None):
+        self.nco, self.nci = nco, nci
+        self.terms = [(int(co), int(ci), np.asarray(q, dtype=np.float64)) for (co, ci, q) in (terms or [])]
+
+    rotated = False
+
+    @staticmethod
+    def from_matrices(mats):
+        """mats [nl][nco][nci] -> the list of its non-zero (co, ci) entries"""
+        mats = np.asarray(mats, dtype=np.float64)
+        nco, nci = mats.shape[1:]
+        return EllMixList(nco, nci, [(co, ci, mats[:, co, ci].copy()) for co in range(nco) for ci in range(nci)
+                                     if np.any(mats[:, co, ci] != 0)])
+
+    def matrices(self, nl):
+        out = np.zeros((nl, self.nco, self.nci))
+        for (co, ci, q) in self.terms:
+            out[:, co, ci] += q
+        return out
+
+    def scaled(self, a):
+        return EllMixList(self.nco, self.nci, [(co, ci, a * q) for (co, ci, q) in self.terms])
+
+    def merged(self):
+        acc = {}
+        for (co, ci, q) in self.terms:
+            acc[(co, ci)] = acc[(co, ci)] + q if (co, ci) in acc else np.array(q, dtype=np.float64)
+        return EllMixList(self.nco, self.nci, [(co, ci, q) for (co, ci), q in sorted(acc.items()) if np.any(q != 0)])
+
+    def __add__(self, other):
+        assert isinstance(other, EllMixList) and (self.nco, self.nci) == (other.nco, other.nci)
+        return EllMixList(self.nco, self.nci, self.terms + other.terms).merged()
+
+    def compose(self, inner):
+        assert self.nci == inner.nco
+        if isinstance(inner, EllMixList):
+            return EllMixList(self.nco, inner.nci, [(co, ci, qa * qb) for (co, cm, qa) in self.terms
+                                                    for (cm2, ci, qb) in inner.terms if cm2 == cm]).merged()
+        out, rot = [], []                                  # mix o matrix-list: the rows of B[ell] scaled by q[ell]
+        for (co, cm, q) in self.terms:
+            for (cm2, ci, B), rb in zip(inner.terms, inner.rot):
+                if cm2 == cm:
+                    out.append((co, ci, q[:, None, None] * B))
+                    rot.append(rb)
+        return EllTermList(self.nco, inner.nci, out, rot).merged()
+
+    def as_termlist(self, Nr, nr=None):
+        """the same map as radial matrices q[ell] * identity (leading nr x nr block)"""
+        nl = len(self.terms[0][2]) if self.terms else 1
+        return self.compose(EllTermList.identity(self.nci, nl, Nr, Nr if nr is None else nr))
 
 
 REG = (-1, +1, 0)
@@ -730,8 +791,13 @@ class ShOperand:
         return NotImplemented
 
     @property
+    def sig(self):
+        """components per tensor index: 3 (phi, theta, r / -, +, 0), or 2 for an S2 index (-, +), which angular() makes"""
+        return getattr(self, "_sig", None) or (3,) * self.rank
+
+    @property
     def ncomp(self):
-        return 3 ** self.rank
+        return int(np.prod(self.sig, dtype=np.int64))
 
     def __add__(self, other):
         return ShAdd.make(self, other)
@@ -795,9 +861,15 @@ class ShOperand:
         return False
 
     def evaluate(self):
-        f = ShellField(self.dist, self.basis, rank=self.rank)
+        f = ShellField(self.dist, self.basis, rank=self.rank, sig=self.sig)
         f._set_device_coeff(self.eval_c())
         return f
+
+
+def _no_s2_index(what, *args):
+    for a in args:
+        if isinstance(a, ShOperand) and any(d != 3 for d in a.sig):
+            raise NotImplementedError("%s of an operand with an S2 index (%r)" % (what, a))
 
 
 class ShReduced(sphreduce.ReducedResult, ShOperand):
@@ -810,6 +882,7 @@ class ShReduced(sphreduce.ReducedResult, ShOperand):
     def __init__(self, arg, **params):
         if not isinstance(arg, ShOperand) or isinstance(arg, (RadialField, ConstField)) or arg.basis is None:
             raise NotImplementedError("%s of an operand without an angular basis" % self.what)
+        _no_s2_index(self.what, arg)
         if isinstance(arg, ShLinear) and arg.kind in ("interp", "integ"):
             raise NotImplementedError("%s of a reduced operand (%s): reductions of reductions are not supported"
                                       % (self.what, arg.kind))
@@ -1031,7 +1104,7 @@ class ShUnary(ShOperand):
 class ShScale(ShOperand):
     def __init__(self, a, arg):
         self.a, self.arg, self.args = float(a), arg, (arg,)
-        self.dist, self.basis, self.rank = arg.dist, arg.basis, arg.rank
+        self.dist, self.basis, self.rank, self._sig = arg.dist, arg.basis, arg.rank, arg.sig
 
     def is_grid_native(self):
         return self.arg.is_grid_native()
@@ -1091,7 +1164,9 @@ class ShAdd(ShOperand):
     def __init__(self, a, b):
         if a.rank != b.rank:
             raise ValueError("cannot add tensors of different rank")
-        self.dist, self.rank = a.dist, a.rank
+        if a.sig != b.sig:
+            raise ValueError("cannot add tensors of different signature: components per index %s and %s" % (a.sig, b.sig))
+        self.dist, self.rank, self._sig = a.dist, a.rank, a.sig
         self.basis = _common_basis(a, b)
         self.args = (_converted(a, self.basis), _converted(b, self.basis))
 
@@ -1141,6 +1216,7 @@ class ShLinear(ShOperand):
     def __init__(self, kind, arg, **kw):
         if not isinstance(arg, ShOperand):
             raise ValueError("%s needs a field operand" % kind)
+        _no_s2_index(kind, arg)
         self.kind, self.arg, self.args, self.kw = kind, arg, (arg,), kw
         self.dist = arg.dist
         ab = arg.basis
@@ -1288,6 +1364,7 @@ class ShProduct(ShOperand):
     it is evaluated on the dealiased grid (MultiplyFields / DotProduct, core/arithmetic.py:586-674)."""
 
     def __init__(self, a, b, contract=False, cross=False):
+        _no_s2_index("product", a, b)
         self.args, self.contract, self.cross = (a, b), contract, cross
         self.dist = a.dist
         if contract and (a.rank < 1 or b.rank < 1):
@@ -1479,6 +1556,167 @@ def cross(a, b):
 Curl, CrossProduct = curl, cross
 
 
+def _spin_selection(kind, sig, **kw):
+    """(P [ncomp_out][ncomp_in], sig_out) on spin (equally: coordinate) components, index tuples over `sig` in C order:
+    the permutation of TransposeComponents (core/operators.py:1916-1934), the selection of S2RadialComponent
+    (core/basis.py:5896-5911: the components whose index `index` is 2, the radial one) or that of S2AngularComponent
+    (:5937-5950: the components whose index is - or +, which becomes an S2 index of two components)."""
+    idx_in = list(np.ndindex(*sig))
+    if kind == "trans":
+        i, j = kw["indices"]
+        sig_out = list(sig)
+        sig_out[i], sig_out[j] = sig[j], sig[i]
+        keep = lambda t: True
+        image = lambda t: tuple(t[j] if a == i else t[i] if a == j else t[a] for a in range(len(t)))
+    elif kind == "radial":
+        index = kw["index"]
+        sig_out = list(sig[:index] + sig[index + 1:])
+        keep = lambda t: t[index] == 2
+        image = lambda t: tuple(t[:index] + t[index + 1:])
+    else:
+        index = kw["index"]
+        sig_out = list(sig[:index] + (2,) + sig[index + 1:])
+        keep = lambda t: t[index] < 2
+        image = lambda t: tuple(t)
+    idx_out = list(np.ndindex(*sig_out))
+    P = np.zeros((len(idx_out), len(idx_in)))
+    for ci, t in enumerate(idx_in):
+        if keep(t):
+            P[idx_out.index(image(t)), ci] = 1.0
+    return P, tuple(sig_out)
+
+
+class ShMix(ShOperand):
+    """trans(T, indices) / radial(T, index) / angular(T, index): a mix of the components of every (m, ell) line, the identity along n.  On the
+    spin components of a surface operand it is the permutation / selection P itself, on the regularity components of a shell
+    operand Q_out(ell)^T P Q_in(ell) (SphericalTransposeComponents, core/operators.py:1984-2045).  The result keeps the
+    operand's basis."""
+
+    def __init__(self, kind, arg, **kw):
+        name = kind
+        if not isinstance(arg, ShOperand):
+            raise ValueError("%s needs a field operand" % name)
+        if isinstance(arg, RadialField):
+            raise NotImplementedError("%s of a radial operand %r" % (name, arg))
+        if isinstance(arg, ConstField) or arg.basis is None:
+            raise NotImplementedError("%s of a constant operand %r" % (name, arg))
+        if isinstance(arg, ShReduced):
+            raise NotImplementedError("%s of a reduced operand (%s)" % (name, arg.what))
+        self.kind, self.arg, self.args, self.kw = kind, arg, (arg,), kw
+        self.dist, self.basis = arg.dist, arg.basis
+        if kind == "trans":
+            i, j = kw["indices"]
+            if arg.rank < 2 or not (0 <= i < arg.rank and 0 <= j < arg.rank):
+                raise ValueError("trans needs a tensor of rank >= 2 and two of its indices")
+            self.rank = arg.rank
+        else:
+            if not 0 <= kw["index"] < arg.rank:
+                raise ValueError("index greater than rank")
+            if arg.sig[kw["index"]] != 3:
+                raise ValueError("%s of an index that is an S2 index already" % kind)
+            self.rank = arg.rank - 1 if kind == "radial" else arg.rank
+        if not isinstance(self.basis, SurfaceBasis) and (kind == "angular" or any(d != 3 for d in arg.sig)):
+            # the reference has AngularComponent on surface operands only (S2AngularComponent, basis_type = SphereBasis), and
+            # there are no Q(ell) for a tensor with an S2 index in the volume
+            raise NotImplementedError("%s of the shell (volume) operand %r: an S2 index exists on surface operands, "
+                                      "take u(r=R0) first" % (kind, arg))
+        self.P, self._sig = _spin_selection(kind, arg.sig, **kw)
+        self._dev = None
+
+    def mixlist(self):
+        """per ell (the subproblem matrices of a left-hand side)"""
+        sb = self.basis.sphere
+        if isinstance(self.basis, SurfaceBasis):
+            mats = np.broadcast_to(self.P, (sb.nl,) + self.P.shape)
+        else:
+            Qo = [sph.intertwiner(ell, self.rank) if self.rank else np.eye(1) for ell in range(sb.nl)]
+            mats = np.array([Qo[ell].T @ self.P @ sph.intertwiner(ell, self.arg.rank) for ell in range(sb.nl)])
+            mats[np.abs(mats) < 1e-14] = 0.0
+        return EllMixList.from_matrices(mats)
+
+    def _slot_mix(self):
+        """(terms (co, ci, q [nq]), slot map [2 nml][nl]) for EVALUATION: a slot that the packed layout covers with several
+        ell boxes is recombined by each of them in turn (ShellBasis.regularity_plan), so its mix is F_out P B_in with the
+        products F, B of those Q(ell)^T, Q(ell)."""
+        sb = self.basis.sphere
+        rows, cols, ok = sb.pack_index()
+        slot_p, _, bwd = curvilinear.recombination_tables(sb.packed_ell_rows(), sb.packed_shape(), self.arg.rank)
+        if isinstance(self.basis, SurfaceBasis):
+            mats = np.broadcast_to(self.P, (len(bwd),) + self.P.shape)
+        else:
+            fwd = curvilinear.recombination_tables(sb.packed_ell_rows(), sb.packed_shape(), self.rank)[1] if self.rank \
+                else np.ones((len(bwd), 1, 1))
+            mats = np.array([fwd[i] @ self.P @ bwd[i] for i in range(len(bwd))])
+            mats[np.abs(mats) < 1e-14] = 0.0
+        slot = -np.ones((2 * sb.nm, sb.nl), dtype=np.int32)
+        slot[rows[ok], cols[ok]] = slot_p[ok]
+        return EllMixList.from_matrices(mats).terms, np.ascontiguousarray(slot[2 * sb.m0:2 * (sb.m0 + sb.nml)])
+
+    def is_grid_native(self):
+        return self.kind != "angular" and self.arg.is_grid_native()
+
+    def grid_native(self):
+        """operands formed on the grid are permuted there (TransposeComponents.operate, core/operators.py:2033-2035)"""
+        if not self.is_grid_native():
+            return None
+        ex = self.dist.executor
+        g = self.arg.grid_native()
+        out = ex.empty((self.ncomp,) + tuple(g.shape[1:]))
+        for co, ci in zip(*np.nonzero(self.P)):
+            ex.assign(out[int(co):int(co) + 1], g[int(ci):int(ci) + 1])
+        return out
+
+    def eval_g(self):
+        return self.grid_native() if self.is_grid_native() else _eval_grid(self)
+
+    def eval_c(self):
+        if self.is_grid_native():
+            return forward(self.dist, self.basis, self.rank, self.grid_native(), self.basis.dealias)
+        ex = self.dist.executor
+        sb = self.basis.sphere
+        if getattr(ex, "make_ell_mix", None) is None:
+            raise NotImplementedError("the executor %r has no component mix (make_ell_mix)" % (ex,))
+        if self._dev is None or self._dev[0] is not ex:
+            terms, slot_map = self._slot_mix()
+            self._dev = (ex, ex.make_ell_mix(sb.nml, sb.nl, self.basis.Nr, self.ncomp, self.arg.ncomp, terms, slot_map))
+        y = ex.empty((self.ncomp, 2 * sb.nml, sb.nl, self.basis.Nr))
+        self._dev[1].apply(self.arg.eval_c(), y)
+        return y
+
+    def lin(self, variables):
+        d, isdt = self.arg.lin(variables)
+        ml = self.mixlist()
+        return {i: ml.compose(t) for i, t in d.items()}, isdt
+
+
+def _tensor_index(a, index):
+    """negative indices count from the last one (Component.__init__, core/operators.py:2201)"""
+    index = int(index)
+    return index + getattr(a, "rank", 0) if index < 0 else index
+
+
+def trans(a, indices=(0, 1)):
+    """TransposeComponents of a shell or surface tensor of rank >= 2 (both indices spherical); the result keeps the basis"""
+    i, j = (_tensor_index(a, i) for i in indices)
+    return ShMix("trans", a, indices=(i, j))
+
+
+def radial(a, index=0):
+    """RadialComponent: drops the tensor index `index`.  The reference defines it on surface operands (u(r=R0)) only; on a
+    shell (volume) operand it is an extension of this code, the same selection between the Q(ell) of the operand and of
+    the result (its test data is the reference's coordinate component, not a reference operator: DESIGN.md section 9)."""
+    return ShMix("radial", a, index=_tensor_index(a, index))
+
+
+def angular(a, index=0):
+    """AngularComponent of a surface operand (u(r=R0)): the index becomes an S2 index of the two components (-, +).  The
+    result serves as boundary rows and as a coefficient-space task; it has no grid data here."""
+    return ShMix("angular", a, index=_tensor_index(a, index))
+
+
+transpose, TransposeComponents, RadialComponent, AngularComponent = trans, trans, radial, angular
+
+
 def dt(a):
     return ShDt(a)
 
@@ -1609,8 +1847,10 @@ class ShellField(HostMirror, ShOperand):
     """Tensor field on a ShellBasis (or one of its surfaces): device-resident data with lazily synchronised host mirrors, `['g']` / `['c']`
     in the reference's shapes (packed (m, ell) coefficient layout, core/basis.py:2839-2891)."""
 
-    def __init__(self, dist, basis, rank=0, name=None):
+    def __init__(self, dist, basis, rank=0, name=None, sig=None):
         self.dist, self.basis, self.rank, self.name = dist, basis, rank, name
+        if sig is not None and tuple(sig) != (3,) * rank:
+            self._sig = tuple(sig)                  # a task with an S2 index (angular): coefficient data only
         self._init_mirror(3)
         self.args = ()
 
@@ -1662,8 +1902,10 @@ class ShellField(HostMirror, ShOperand):
         self._g = None
 
     def _global_shape(self, layout, scales):
-        t = (3,) * self.rank
+        t = tuple(self.sig)
         if layout == "g":
+            if t != (3,) * self.rank:
+                raise NotImplementedError("grid data of a field with an S2 index (angular)")
             return t + self.basis.grid_shape(scales)
         return t + self.basis.sphere.packed_shape() + (self.basis.Nr,)
 
@@ -1773,7 +2015,9 @@ class ShellProblem(CurvilinearProblem):
     operand_type, add_type, scale_type = ShOperand, ShAdd, ShScale
     operators = dict(lap=lap, grad=grad, div=div, dt=dt, Lift=Lift, lift=Lift, trace=trace, integ=integ,
                      Laplacian=lap, Gradient=grad, Divergence=div, TimeDerivative=dt, Trace=trace,
-                     Integrate=integ, ave=ave, Average=ave, curl=curl, Curl=curl, cross=cross, CrossProduct=cross)
+                     Integrate=integ, ave=ave, Average=ave, curl=curl, Curl=curl, cross=cross, CrossProduct=cross,
+                     trans=trans, transpose=trans, TransposeComponents=trans, radial=radial, RadialComponent=radial,
+                     angular=angular, AngularComponent=angular)
 
     def __init__(self, variables, namespace=None, time="t"):
         super().__init__(variables, namespace, time)
@@ -1820,14 +2064,14 @@ class _EllPack:
         self.mats[mid].apply(x, y)
 
 
-def _valid_modes(basis, rank, nl, Nr):
+def _valid_modes(basis, sig, nl, Nr):
     """[ncomp][nl][Nr] validity of (component, ell, n): regularity components of a shell field, spin components of
-    a surface field (n = 0 only)."""
-    out = np.zeros((3 ** rank, nl, Nr), dtype=bool)
+    a surface field (n = 0 only; an S2 index has the components -, + alone)."""
+    out = np.zeros((int(np.prod(sig, dtype=np.int64)), nl, Nr), dtype=bool)
     if basis is None:                       # constants: the (ell = 0, n = 0) mode only
         out[0, 0, 0] = True
         return out
-    for c, idx in enumerate(reg_indices(rank)):
+    for c, idx in enumerate(np.ndindex(*sig)):
         for ell in range(nl):
             if isinstance(basis, SurfaceBasis):
                 out[c, ell, 0] = spin_allowed(ell, idx)
@@ -1860,8 +2104,8 @@ class ShellSolverBase:
         if nv != ne or Re != self.R:
             raise ValueError("the problem is not square: %d equation rows for %d unknowns per (m, ell)" % (ne, nv))
         self.nx, self.ny = 2 * self.nm, self.nl * self.Nr          # timestepper buffers: (R, nx, ny) elements
-        self.col_valid = self._packed_valid([(v.basis, v.rank) for v in self.variables], self.vmap)
-        self.row_valid = self._packed_valid([(eq["basis"], eq["rank"]) for eq in problem.equations], self.emap)
+        self.col_valid = self._packed_valid([(v.basis, v.sig) for v in self.variables], self.vmap)
+        self.row_valid = self._packed_valid([(eq["basis"], eq["lhs"].sig) for eq in problem.equations], self.emap)
         self.M_tl = self._system_termlist("M")
         self.L_tl = self._system_termlist("L")
         self.pack = _EllPack()
@@ -1893,8 +2137,8 @@ class ShellSolverBase:
 
     def _packed_valid(self, items, maps):
         valid = np.zeros((self.R, self.nl, self.Nr), dtype=bool)
-        for (basis, rank), m in zip(items, maps):
-            v = _valid_modes(basis, rank, self.nl, self.Nr)
+        for (basis, sig), m in zip(items, maps):
+            v = _valid_modes(basis, sig, self.nl, self.Nr)
             for c, (sc, off, nr) in enumerate(m):
                 valid[sc, :, off:off + nr] = v[c, :, :nr]
         return valid

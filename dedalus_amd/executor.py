@@ -481,6 +481,11 @@ class HipExecutor:
             return EllTermsCx(self, nm, nl, nr, ncomp_out, terms, slot_map, rot)
         return EllTerms(self, nm, nl, nr, ncomp_out, terms, slot_map)
 
+    def make_ell_mix(self, nm, nl, nr, ncomp_out, ncomp_in, terms, slot_map=None):
+        """terms: list of (co, ci, q [nq]) with one real scalar per slot id; slot_map [2 nm][nl] -> row of q or -1 (default:
+        ell where ell >= m) -> device component mix, the identity along n (ddh_ell_mix_create)."""
+        return EllMix(self, nm, nl, nr, ncomp_out, ncomp_in, terms, slot_map)
+
     def make_cgemv_batch(self, nm, nl, ncomp, mats):
         """mats: per m a complex (n_m, n_m) array, n_m = ncomp * max(nl - m, 0)."""
         return CgemvBatch(self, nm, nl, ncomp, mats)
@@ -864,6 +869,47 @@ class EllTermsCx:
             raise ValueError("ell terms: contiguous operands only")
         libhip.note_cost("ddh_ell_terms_apply_cx", 2.0 * self._madds, self._mat_bytes + (x.numel() + y.numel()) * 8)
         libhip.call("ddh_ell_terms_apply_cx", self.handle, ptr(x), ptr(y), self.ex.dev.stream)
+
+    def __del__(self):
+        try:
+            libhip.call("ddh_destroy", self.handle)
+        except Exception:
+            pass
+
+
+class EllMix:
+    """Device component mix of shell tensor fields (transpose, radial and angular components): one streaming launch."""
+
+    def __init__(self, ex, nm, nl, nr, ncomp_out, ncomp_in, terms, slot_map):
+        self.ex = ex
+        terms = sorted(terms, key=lambda t: (t[0], t[1]))
+        co = np.ascontiguousarray([t[0] for t in terms], dtype=np.int32)
+        ci = np.ascontiguousarray([t[1] for t in terms], dtype=np.int32)
+        sm = np.ascontiguousarray(default_slot_map(nm, nl) if slot_map is None else slot_map, dtype=np.int32)
+        if sm.shape != (2 * nm, nl):
+            raise ValueError("slot map must be [2 nm][nl]")
+        nq = int(np.asarray(terms[0][2]).size) if terms else max(int(sm.max()) + 1, 1)
+        q = np.zeros((max(len(terms), 1), nq))
+        for i, t in enumerate(terms):
+            q[i] = np.asarray(t[2], dtype=np.float64).reshape(nq)
+        self.shape_in = (int(ncomp_in), 2 * nm, nl, nr)
+        self.shape_out = (int(ncomp_out), 2 * nm, nl, nr)
+        self.handle = C.c_uint64(0)
+        libhip.call("ddh_ell_mix_create", C.byref(self.handle), int(nm), int(nl), int(nr), int(ncomp_out), int(ncomp_in),
+                    len(terms), libhip.as_ip(co), libhip.as_ip(ci), nq, libhip.as_dp(q), libhip.as_ip(sm))
+        live = int(np.count_nonzero(sm >= 0))
+        read = len({int(c) for c in ci})
+        self._madds = float(len(terms)) * live * nr
+        self._bytes = 8.0 * nr * (live * read + sm.size * int(ncomp_out))
+
+    def apply(self, x, y):
+        if tuple(x.shape) != self.shape_in or tuple(y.shape) != self.shape_out:
+            raise ValueError("ell mix: operand shapes %s -> %s do not match the mix (%s -> %s)"
+                             % (tuple(x.shape), tuple(y.shape), self.shape_in, self.shape_out))
+        if not (x.is_contiguous() and y.is_contiguous()):
+            raise ValueError("ell mix: contiguous operands only")
+        libhip.note_cost("ddh_ell_mix_apply", 2.0 * self._madds, self._bytes)
+        libhip.call("ddh_ell_mix_apply", self.handle, ptr(x), ptr(y), self.ex.dev.stream)
 
     def __del__(self):
         try:

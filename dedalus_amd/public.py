@@ -52,6 +52,19 @@ grad, div, lap, skew, ave, dt, trace, integ, curl, cross = (_dispatch(n, c) for 
 Curl = curl
 CrossProduct = _dispatch("cross", CrossProduct)
 Average = _dispatch("ave", Average)          # Average(f, coords['phi']) of sphere / shell operands; else the Cartesian class
+trans = _dispatch("trans", transpose)          # shell operands: SphericalTransposeComponents; else the Cartesian transpose
+transpose = _dispatch("trans", transpose)
+TransposeComponents = _dispatch("trans", TransposeComponents)
+
+
+def _no_components(name):
+    def cart(operand, index=0, **kw):
+        raise NotImplementedError("%s of %r: defined for operands in spherical coordinates" % (name, operand))
+    return cart
+
+
+radial = RadialComponent = _dispatch("radial", _no_components("radial"))
+angular = AngularComponent = _dispatch("angular", _no_components("angular"))
 MulCosine = _sphere.MulCosine
 _CartesianIVP, _CartesianLBVP = IVP, LBVP
 

@@ -234,6 +234,19 @@ int ddh_ell_terms_create_cx(ddh_handle *h, int nm, int nl, int nr, int ncomp_out
                             const int *co_h, const int *ci_h, const int *rot_h, int nmat, const double *mats_h,
                             const int *slot_map_h);
 int ddh_ell_terms_apply_cx(ddh_handle h, const double *x, double *y, void *stream);
+/* Component mixes of shell tensor fields (transpose, radial and angular components): the identity along n, one real scalar
+ * per term and slot id,  y[co][i1][ell][:] = sum_t q_h[t][id] x[ci_t][i1][ell][:],  id = slot_map_h[i1][ell] in [0, nq);
+ * q_h is [nterms][nq], term-major (id: the ell of the slot, or one of the extra ids past nl for the slots that the packed
+ * layout covers with several ell boxes).  nterms <= 4096.
+ * In regularity components q = Q_out(ell)^T P Q_in(ell) with P the permutation / selection of spin components: replaces
+ * SphericalTransposeComponents.subproblem_matrix / operate (core/operators.py:1993-2045) and, with P alone on spin
+ * components, S2RadialComponent / S2AngularComponent (core/basis.py:5892-5969).  Terms sorted by co; the terms of an
+ * output component are summed in term order in one launch, without atomics.  A slot with slot_map_h < 0 is never read
+ * and receives +0.  16-byte accesses when nr is even and x, y are 16-byte aligned.  ncomp_in: components of x;
+ * 68 (nterms + 2) + 4096 ncomp_in + 4 ncomp_out bytes of LDS must fit 160 KiB.                                                          */
+int ddh_ell_mix_create(ddh_handle *h, int nm, int nl, int nr, int ncomp_out, int ncomp_in, int nterms, const int *co_h,
+                       const int *ci_h, int nq, const double *q_h, const int *slot_map_h);
+int ddh_ell_mix_apply(ddh_handle h, const double *x, double *y, void *stream);
 
 /* ---- device factorization of the curvilinear subproblems (SURVEY 8a row a9 for configs S and H) ------------------
  * (a M + b L)^-1 for a batch of small dense systems (n <= 1024), real or complex, formed and inverted ON THE DEVICE
