@@ -1289,14 +1289,12 @@ class ShLinear(ShOperand):
             seqs, slot_map = operate_slot_sequences(sb)
             terms = [(co, ci, np.concatenate([m] + [sum(m[l] for l in seq)[None] for seq in seqs])) for (co, ci, m) in tl.terms]
             slot_map = np.array(slot_map[2 * sb.m0:2 * (sb.m0 + sb.nml)])       # a copy: the cached map is shared by all operators
-            if tl.rotated:
+            if tl.rotated and sb.m0 == 0:
                 # the msin part of (m, ell) = (0, 0) is no mode of a vector (valid_elements, core/basis.py:4299-4305): the
                 # rotation must not carry it into the cos part
-                if sb.m0 == 0:
-                    slot_map[1, 0] = -1
-                self._dev = (ex, ex.make_ell_terms(sb.nml, sb.nl, shell.Nr, tl.nco, terms, slot_map, rot=tl.rot))
-            else:
-                self._dev = (ex, ex.make_ell_terms(sb.nml, sb.nl, shell.Nr, tl.nco, terms, slot_map))
+                slot_map[1, 0] = -1
+            rot = dict(rot=tl.rot) if tl.rotated else {}        # (the NumPy oracle executor knows no rotated terms)
+            self._dev = (ex, ex.make_ell_terms(sb.nml, sb.nl, shell.Nr, tl.nco, terms, slot_map, **rot))
         x = _padded(ex, self.arg.eval_c(), shell.Nr)
         y = ex.empty((self.ncomp, 2 * sb.nml, sb.nl, shell.Nr))
         self._dev[1].apply(x, y)

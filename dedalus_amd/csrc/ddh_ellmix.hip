@@ -112,16 +112,9 @@ int ddh_ell_mix_create(ddh_handle *h, int nm, int nl, int nr, int ncomp_out, int
     }
     for (long i = 0; i < 2L * nm * nl; ++i)
         if (slot_map_h[i] >= nq) return fail("ell_mix_create: slot map points past the coefficient rows");
-    std::vector<int> ci(ntp, 0), first(ncomp_out + 1, 0);
-    for (int t = 0; t < nterms; ++t) {
-        if (co_h[t] < 0 || co_h[t] >= ncomp_out || (t > 0 && co_h[t] < co_h[t - 1]))
-            return fail("ell_mix_create: terms must be sorted by output component");
-        if (ci_h[t] < 0 || ci_h[t] >= ncomp_in) return fail("ell_mix_create: input component out of range");
-        ci[t] = ci_h[t];
-        first[co_h[t] + 1] = t + 1;
-    }
-    for (int c = 0; c < ncomp_out; ++c)
-        if (first[c + 1] < first[c]) first[c + 1] = first[c];
+    std::vector<int> ci(ntp, 0), first;
+    if (int st = term_table("ell_mix_create", nterms, co_h, ci_h, ncomp_out, ncomp_in, first)) return st;
+    for (int t = 0; t < nterms; ++t) ci[t] = ci_h[t];
     std::vector<double> q((size_t)nq * ntp, 0.0);         // [nterms][nq] -> [nq][ntp]
     for (int t = 0; t < nterms; ++t)
         for (int i = 0; i < nq; ++i) q[(size_t)i * ntp + t] = q_h[(size_t)t * nq + i];

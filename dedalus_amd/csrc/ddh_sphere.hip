@@ -161,23 +161,29 @@ cgemv_batch_kernel(const double *__restrict__ x, double *__restrict__ y, const l
 
 // ------------------------------------------------------------------------------------------------
 // ell-dependent radial operators of shell fields (csrc of core/shell.py): fields are
-// [component][2 m + part][ell][n]; a term maps component ci to co through a real matrix A_t[ell] (n_out x n_in),
-// the same for every m and part:  y[co][i1][ell][:] = sum_t A_t[ell] x[ci_t][i1][ell][:].
-// This is SphericalEllOperator.operate / subproblem_matrix (core/operators.py:3108-3222: per (m, ell)
-// apply_matrix of a radial matrix in a Python loop over ell_maps) for all slots in one launch, and -- with
-// the per-ell LHS inverses as the matrices -- the per-ell solve of the shell's subproblems.
+// [component][2 m + part][ell][n], part 0 / 1 = cos / msin of the azimuthal mode m: one complex number z = cos + i msin
+// per (component, m, ell, n).  A term t maps component ci to co through a REAL radial matrix A_t[id] (n_out x n_in; id =
+// slot_map[2 m + part][ell], the default is ell for every m and part) and carries a flag rot_t:
+//     rot_t = 0:  y[co][2m + p] += A x[ci][2m + p]
+//     rot_t = 1:  the term is i A:  y[co][2m + 0] += -A x[ci][2m + 1],  y[co][2m + 1] += +A x[ci][2m + 0]
+// The first is SphericalEllOperator.operate / subproblem_matrix (core/operators.py:3108-3222: per (m, ell) apply_matrix
+// of a radial matrix in a Python loop over ell_maps) for all slots in one launch, and -- with the per-ell LHS inverses
+// as the matrices -- the per-ell solve of the shell's subproblems.  The second is (i A)(c + i s) = -A s + i A c, the
+// real-dtype branch of SphericalCurl.operate (core/operators.py:3944-3978: vec_in_cos + 1j * vec_in_msin through the
+// purely imaginary radial matrices of :3889-3901, real part to the cos rows, imaginary part to the msin rows).
 
 struct EllTerms : HandleBase {
     int nm = 0, nl = 0, nr = 0, ncomp_out = 0, nterms = 0, nmat = 0;
-    int *d_meta = nullptr;       // [nterms][2]: co, ci (sorted by co)
+    int *d_meta = nullptr;       // [nterms][3]: co, ci, rot (sorted by co)
     int *d_first = nullptr;      // [ncomp_out + 1]
     int *d_slot = nullptr;       // [2 nm][nl]: matrix index of the slot, -1: no mode
     short *d_band = nullptr;     // [nterms][nmat][nr][2]: first / one-past-last non-zero column of every row
     short *d_rows = nullptr;     // [nterms][nmat][2]: first / one-past-last non-zero row
     double *d_mats = nullptr;    // [nterms][nmat][n_in][n_out]  (transposed: threads run along n_out)
     int *d_tmap = nullptr;       // dense path: [ncomp_out][ncomp_in] -> term index or -1
-    int dense = 0;               // 1: mostly full blocks, default slot map -> per-ell FP64 MFMA GEMM
+    int dense = 0;               // 1: mostly full blocks, default slot map, no rotated term -> per-ell FP64 MFMA GEMM
     int ncomp_in = 0;
+    bool rotated = false;        // some term has rot = 1
     ~EllTerms() override {
         (void)hipFree(d_meta);
         (void)hipFree(d_first);
@@ -269,14 +275,111 @@ ell_gemm_kernel(const double *__restrict__ x, double *__restrict__ y, const int 
     }
 }
 
-// One workgroup = ELL_S consecutive (m, part) slots of one ell, threads run along the output radial index.  The
-// input rows of all components are staged once in LDS ([component][n][slot], so a thread reads its ELL_S
-// right-hand sides with one wide LDS load per n); every matrix element fetched from L2/HBM is used ELL_S times.
-// Per term and matrix the band offsets (kl, ku) of the non-zeros bound the inner loop: differential operators are
-// banded in n, the LHS inverses are dense.
-constexpr int ELL_S = 8;     // slots per workgroup
+// Banded term lists (differential operators, and every list with a rotated term).  Launch shape (the edges
+// tests/shell_vector_cases.py lists): one workgroup = ELL_S = 8 consecutive slots (4 azimuthal pairs, so both parts of a
+// pair always sit in one workgroup) of one ell; threadIdx.x runs along the output radial index (64, 128 or 256 threads:
+// nr <= 64, <= 255, >= 256), threadIdx.y over ELL_CO = 4 output components at a time.  The input lines of all components
+// are staged once in LDS as [component][n][slot]: a thread then reads the 8 right-hand sides of one n with two 32-byte
+// LDS loads, and every matrix element fetched from L2 / HBM is used 8 times.  The matrices are stored transposed
+// ([n_in][n_out]).  Differential operators are banded in n: per term, matrix and output row the first / one-past-last
+// non-zero column bounds the inner loop (and a row range per term and matrix skips the empty rows of a block), so the
+// kernel streams the lines once.  In that regime every lane starts its loop at its own row's first column: at one
+// iteration neighbouring lanes read neighbouring LDS lines (64 bytes apart: two lanes per bank group, not a broadcast)
+// and matrix elements nr + 1 doubles apart (the diagonals of the transposed matrix); only rows that are full (dense
+// blocks) give the broadcast / consecutive pattern.  profiles/shell_vector_ops.txt holds the rates of grad and curl.
+//
+// ROT = false is the instance of lists without a rotated term: it neither reads the flag nor branches on it.
+//
+// A slot with slot_map < 0 carries no mode: it is never read -- not as the rotation partner of its pair either, where it
+// contributes nothing -- and exact +0 is written to it.  No atomics: every output element is summed by one thread in
+// the order (term, n_in ascending), a function of the term list alone.
+constexpr int ELL_S = 8;     // slots per workgroup (even: a (cos, msin) pair never straddles two workgroups)
 constexpr int ELL_CO = 4;    // output components processed concurrently (threadIdx.y)
 
+// The output rows of one workgroup.  SAME: every live slot of the group uses matrix mid0 (the rule); else the slots of the
+// group use different matrices (rare).  The kernel branches once per workgroup between the two instances, so the
+// registers and loop bounds of the rare one stay out of the common one.
+template <bool ROT, bool SAME>
+__device__ __forceinline__ void ell_terms_rows(const double *__restrict__ sx, double *__restrict__ y,
+                                               const int *__restrict__ meta, const int *__restrict__ first,
+                                               const short *__restrict__ band, const short *__restrict__ rows,
+                                               const double *__restrict__ mats, const int (&mid)[ELL_S], int mid0, int i0, int l,
+                                               int nm, int nl, int nr, int nmat, int ncomp_out) {
+    const long cstride = 2L * nm * nl * nr;
+    for (int co = threadIdx.y; co < ncomp_out; co += ELL_CO) {
+        for (int no = threadIdx.x; no < nr; no += blockDim.x) {
+            double acc[ELL_S];
+#pragma unroll
+            for (int s = 0; s < ELL_S; ++s) acc[s] = 0.0;
+            for (int t = first[co]; t < first[co + 1]; ++t) {
+                const int ci = meta[3 * t + 1];
+                const bool rot = ROT && meta[3 * t + 2];
+                const double *xs = sx + (long)ci * nr * ELL_S;
+                if (SAME) {
+                    if (!ROT) {                       // (not for lists with rotated terms: the curl's blocks have no empty
+                        const long ri = 2 * ((long)t * nmat + mid0);        // rows, and this is one more dependent load per term)
+                        if (no < rows[ri] || no >= rows[ri + 1]) continue;  // this row of the block is empty
+                    }
+                    const long bi = 2 * (((long)t * nmat + mid0) * nr + no);
+                    const int n0 = band[bi], n1 = band[bi + 1];          // non-zero columns of this row
+                    const double *A = mats + (((long)t * nmat + mid0) * nr) * nr + no;
+                    if (rot) {
+                        for (int ni = n0; ni < n1; ++ni) {
+                            const double a = A[(long)ni * nr];
+                            const double4 xv = *reinterpret_cast<const double4 *>(xs + (long)ni * ELL_S);
+                            const double4 xw = *reinterpret_cast<const double4 *>(xs + (long)ni * ELL_S + 4);
+                            acc[0] -= a * xv.y;
+                            acc[1] += a * xv.x;
+                            acc[2] -= a * xv.w;
+                            acc[3] += a * xv.z;
+                            acc[4] -= a * xw.y;
+                            acc[5] += a * xw.x;
+                            acc[6] -= a * xw.w;
+                            acc[7] += a * xw.z;
+                        }
+                    } else {
+                        for (int ni = n0; ni < n1; ++ni) {
+                            const double a = A[(long)ni * nr];
+                            const double4 xv = *reinterpret_cast<const double4 *>(xs + (long)ni * ELL_S);
+                            const double4 xw = *reinterpret_cast<const double4 *>(xs + (long)ni * ELL_S + 4);
+                            acc[0] += a * xv.x;
+                            acc[1] += a * xv.y;
+                            acc[2] += a * xv.z;
+                            acc[3] += a * xv.w;
+                            acc[4] += a * xw.x;
+                            acc[5] += a * xw.y;
+                            acc[6] += a * xw.z;
+                            acc[7] += a * xw.w;
+                        }
+                    }
+                } else {
+                    // The loop is bounded by the row's band as above: for finite input this gives the bits of a loop over
+                    // all nr columns, whose further products are 0 * x added to an accumulator that starts at +0 (and so
+                    // never holds -0)
+#pragma unroll
+                    for (int s = 0; s < ELL_S; ++s) {
+                        if (mid[s] < 0) continue;
+                        const long bi = 2 * (((long)t * nmat + mid[s]) * nr + no);
+                        const int n0 = band[bi], n1 = band[bi + 1];
+                        const double *A = mats + (((long)t * nmat + mid[s]) * nr) * nr + no;
+                        if (ROT) {
+                            const int sp = rot ? (s ^ 1) : s;          // the slot read: the other part of the pair for i A
+                            const double sg = (rot && !(s & 1)) ? -1.0 : 1.0;
+                            for (int ni = n0; ni < n1; ++ni) acc[s] += sg * (A[(long)ni * nr] * xs[(long)ni * ELL_S + sp]);
+                        } else {
+                            for (int ni = n0; ni < n1; ++ni) acc[s] += A[(long)ni * nr] * xs[(long)ni * ELL_S + s];
+                        }
+                    }
+                }
+            }
+#pragma unroll
+            for (int s = 0; s < ELL_S; ++s)
+                if (i0 + s < 2 * nm) y[co * cstride + ((long)(i0 + s) * nl + l) * nr + no] = (mid[s] >= 0) ? acc[s] : 0.0;
+        }
+    }
+}
+
+template <bool ROT>
 __global__ void __launch_bounds__(1024)
 ell_terms_kernel(const double *__restrict__ x, double *__restrict__ y, const int *__restrict__ meta,
                  const int *__restrict__ first, const int *__restrict__ slot_map, const short *__restrict__ band,
@@ -306,7 +409,7 @@ ell_terms_kernel(const double *__restrict__ x, double *__restrict__ y, const int
                     if (i0 + s < 2 * nm) y[co * cstride + ((long)(i0 + s) * nl + l) * nr + no] = 0.0;
         return;
     }
-    for (int w = tlin; w < ncomp_in * nr; w += tall) {
+    for (int w = tlin; w < ncomp_in * nr; w += tall) {   // stage the live input lines, +0 for the others
         const int ci = w / nr, ni = w - ci * nr;
 #pragma unroll
         for (int s = 0; s < ELL_S; ++s) {
@@ -315,47 +418,16 @@ ell_terms_kernel(const double *__restrict__ x, double *__restrict__ y, const int
         }
     }
     __syncthreads();
-    for (int co = threadIdx.y; co < ncomp_out; co += ELL_CO) {
-        for (int no = threadIdx.x; no < nr; no += blockDim.x) {
-            double acc[ELL_S];
-#pragma unroll
-            for (int s = 0; s < ELL_S; ++s) acc[s] = 0.0;
-            for (int t = first[co]; t < first[co + 1]; ++t) {
-                const int ci = meta[2 * t + 1];
-                const double *xs = sx + (long)ci * nr * ELL_S;
-                if (same) {
-                    const long ri = 2 * ((long)t * nmat + mid0);
-                    if (no < rows[ri] || no >= rows[ri + 1]) continue;      // this row of the block is empty
-                    const long bi = 2 * (((long)t * nmat + mid0) * nr + no);
-                    const int n0 = band[bi], n1 = band[bi + 1];          // non-zero columns of this row
-                    const double *A = mats + (((long)t * nmat + mid0) * nr) * nr + no;
-                    for (int ni = n0; ni < n1; ++ni) {
-                        const double a = A[(long)ni * nr];
-                        const double4 xv = *reinterpret_cast<const double4 *>(xs + (long)ni * ELL_S);
-                        const double4 xw = *reinterpret_cast<const double4 *>(xs + (long)ni * ELL_S + 4);
-                        acc[0] += a * xv.x;
-                        acc[1] += a * xv.y;
-                        acc[2] += a * xv.z;
-                        acc[3] += a * xv.w;
-                        acc[4] += a * xw.x;
-                        acc[5] += a * xw.y;
-                        acc[6] += a * xw.z;
-                        acc[7] += a * xw.w;
-                    }
-                } else {                              // slots of the group use different matrices (rare)
-#pragma unroll
-                    for (int s = 0; s < ELL_S; ++s) {
-                        if (mid[s] < 0) continue;
-                        const double *A = mats + (((long)t * nmat + mid[s]) * nr) * nr + no;
-                        for (int ni = 0; ni < nr; ++ni) acc[s] += A[(long)ni * nr] * xs[(long)ni * ELL_S + s];
-                    }
-                }
-            }
-#pragma unroll
-            for (int s = 0; s < ELL_S; ++s)
-                if (i0 + s < 2 * nm) y[co * cstride + ((long)(i0 + s) * nl + l) * nr + no] = (mid[s] >= 0) ? acc[s] : 0.0;
-        }
-    }
+    if (same) ell_terms_rows<ROT, true>(sx, y, meta, first, band, rows, mats, mid, mid0, i0, l, nm, nl, nr, nmat, ncomp_out);
+    else ell_terms_rows<ROT, false>(sx, y, meta, first, band, rows, mats, mid, mid0, i0, l, nm, nl, nr, nmat, ncomp_out);
+}
+
+// DDH_ELL_NO_GEMM (measurements): term lists that qualify for the GEMM take the banded kernel.  Read when a handle is
+// created, not when it is applied: creation must know which kernel the handle takes to check and opt in to its LDS.
+// (Handles of ddh_ell_terms_create_dense hold no banded data and always run the GEMM.)
+static bool ell_no_gemm() {
+    static const bool v = getenv("DDH_ELL_NO_GEMM") != nullptr;
+    return v;
 }
 
 }  // namespace ddh
@@ -390,20 +462,14 @@ int ddh_spin_recombine(const double *in, double *out, int ncomp, long npairs, lo
 int ddh_sphere_terms_create(ddh_handle *h, int nm, int nl, int ncomp_out, int nterms, const int *co_h, const int *ci_h,
                             const int *d_h, const double *coef_h) {
     if (nm < 1 || nl < 1 || ncomp_out < 1 || nterms < 0) return fail("sphere_terms_create: bad sizes");
+    std::vector<int> meta(3 * (size_t)(nterms > 0 ? nterms : 1)), first;
+    if (int st = term_table("sphere_terms_create", nterms, co_h, ci_h, ncomp_out, INT_MAX, first)) return st;
+    for (int t = 0; t < nterms; ++t) {
+        meta[3 * t] = co_h[t]; meta[3 * t + 1] = ci_h[t]; meta[3 * t + 2] = d_h[t];
+    }
     SphereTerms *p = new SphereTerms();
     p->kind = H_STERMS;
     p->nm = nm; p->nl = nl; p->ncomp_out = ncomp_out; p->nterms = nterms;
-    std::vector<int> meta(3 * (size_t)(nterms > 0 ? nterms : 1)), first(ncomp_out + 1, 0);
-    for (int t = 0; t < nterms; ++t) {
-        if (co_h[t] < 0 || co_h[t] >= ncomp_out || (t > 0 && co_h[t] < co_h[t - 1])) {
-            delete p;
-            return fail("sphere_terms_create: terms must be sorted by output component");
-        }
-        meta[3 * t] = co_h[t]; meta[3 * t + 1] = ci_h[t]; meta[3 * t + 2] = d_h[t];
-        first[co_h[t] + 1] = t + 1;
-    }
-    for (int c = 0; c < ncomp_out; ++c)
-        if (first[c + 1] < first[c]) first[c + 1] = first[c];
     const size_t cb = (size_t)(nterms > 0 ? nterms : 1) * nm * nl * sizeof(double2);
     if (check_hip(hipMalloc((void **)&p->d_meta, meta.size() * sizeof(int)), "hipMalloc") ||
         check_hip(hipMalloc((void **)&p->d_first, first.size() * sizeof(int)), "hipMalloc") ||
@@ -429,33 +495,28 @@ int ddh_sphere_terms_apply(ddh_handle h, const double *x, double *y, void *strea
     return 0;
 }
 
-int ddh_ell_terms_create(ddh_handle *h, int nm, int nl, int nr, int ncomp_out, int nterms, const int *co_h,
-                         const int *ci_h, int nmat, const double *mats_h, const int *slot_map_h) {
-    if (nm < 1 || nl < 1 || nr < 1 || ncomp_out < 1 || nterms < 0 || nmat < 1) return fail("ell_terms_create: bad sizes");
+int ddh_ell_terms_create(ddh_handle *h, int nm, int nl, int nr, int ncomp_out, int ncomp_in, int nterms, const int *co_h,
+                         const int *ci_h, const int *rot_h, int nmat, const double *mats_h, const int *slot_map_h) {
+    if (nm < 1 || nl < 1 || nr < 1 || nr > 32767 || ncomp_out < 1 || ncomp_in < 1 || nterms < 0 || nmat < 1)
+        return fail("ell_terms_create: bad sizes");
     for (long i = 0; i < 2L * nm * nl; ++i)
         if (slot_map_h[i] >= nmat) return fail("ell_terms_create: slot map points past the matrices");
-    EllTerms *p = new EllTerms();
-    p->kind = H_ELLT;
-    p->nm = nm; p->nl = nl; p->nr = nr; p->ncomp_out = ncomp_out; p->nterms = nterms; p->nmat = nmat;
-    std::vector<int> meta(2 * (size_t)(nterms > 0 ? nterms : 1)), first(ncomp_out + 1, 0);
+    const size_t nt = (size_t)(nterms > 0 ? nterms : 1);
+    std::vector<int> meta(3 * nt, 0), first;
+    if (int st = term_table("ell_terms_create", nterms, co_h, ci_h, ncomp_out, ncomp_in, first)) return st;
+    bool rotated = false;
     for (int t = 0; t < nterms; ++t) {
-        if (co_h[t] < 0 || co_h[t] >= ncomp_out || (t > 0 && co_h[t] < co_h[t - 1])) {
-            delete p;
-            return fail("ell_terms_create: terms must be sorted by output component");
-        }
-        meta[2 * t] = co_h[t]; meta[2 * t + 1] = ci_h[t];
-        first[co_h[t] + 1] = t + 1;
-        if (ci_h[t] + 1 > p->ncomp_in) p->ncomp_in = ci_h[t] + 1;
+        const int rot = rot_h ? rot_h[t] : 0;
+        if (rot != 0 && rot != 1) return fail("ell_terms_create: rot must be 0 or 1");
+        meta[3 * t] = co_h[t]; meta[3 * t + 1] = ci_h[t]; meta[3 * t + 2] = rot;
+        rotated = rotated || rot;
     }
-    if (p->ncomp_in < 1) p->ncomp_in = 1;
-    for (int c = 0; c < ncomp_out; ++c)
-        if (first[c + 1] < first[c]) first[c + 1] = first[c];
     const size_t per = (size_t)nmat * nr * nr;
-    const size_t mb = (size_t)(nterms > 0 ? nterms : 1) * per * sizeof(double);
+    const size_t mb = nt * per * sizeof(double);
     // transpose every matrix to [n_in][n_out]
-    std::vector<double> tr((size_t)(nterms > 0 ? nterms : 1) * per, 0.0);
-    std::vector<short> band(2 * (size_t)(nterms > 0 ? nterms : 1) * nmat * nr, 0);
-    std::vector<short> rows(2 * (size_t)(nterms > 0 ? nterms : 1) * nmat, 0);
+    std::vector<double> tr(nt * per, 0.0);
+    std::vector<short> band(2 * nt * nmat * nr, 0);
+    std::vector<short> rows(2 * nt * nmat, 0);
     for (size_t t = 0; t < (size_t)nterms; ++t)
         for (size_t l = 0; l < (size_t)nmat; ++l) {
             int r0 = nr, r1 = 0;
@@ -481,28 +542,40 @@ int ddh_ell_terms_create(ddh_handle *h, int nm, int nl, int nr, int ncomp_out, i
             rows[2 * (t * nmat + l)] = (short)r0;
             rows[2 * (t * nmat + l) + 1] = (short)r1;
         }
-    // dense path: default slot map (matrix index = ell), rows mostly full, sizes that tile
-    {
-        // (nmat == 1: one matrix shared by every ell -- the radial transforms as GEMMs -- with the default liveness)
-        bool def_map = (nmat == nl || nmat == 1);
-        for (int i1 = 0; def_map && i1 < 2 * nm; ++i1)
-            for (int l = 0; l < nl; ++l) {
-                const int want = ((i1 >> 1) <= l) ? (nmat == 1 ? 0 : l) : -1;
-                if (slot_map_h[i1 * nl + l] != want) { def_map = false; break; }
-            }
-        double fill = 0.0;
-        for (size_t i = 0; i < band.size() / 2; ++i) fill += band[2 * i + 1] - band[2 * i];
-        fill /= (double)(band.size() / 2) * nr;
-        p->dense = def_map && nterms > 0 && fill > 0.5 && nr % EG_K == 0 && (ncomp_out * nr) % EG_M == 0;
-        std::vector<int> tmap((size_t)ncomp_out * p->ncomp_in, -1);
-        for (int t = 0; t < nterms; ++t) tmap[(size_t)co_h[t] * p->ncomp_in + ci_h[t]] = t;
-        if (check_hip(hipMalloc((void **)&p->d_tmap, tmap.size() * sizeof(int)), "hipMalloc") ||
-            check_hip(hipMemcpy(p->d_tmap, tmap.data(), tmap.size() * sizeof(int), hipMemcpyHostToDevice), "hipMemcpy")) {
-            delete p;
-            return -2;
+    // dense path: default slot map (matrix index = ell), rows mostly full, sizes that tile, no rotated term
+    // (nmat == 1: one matrix shared by every ell -- the radial transforms as GEMMs -- with the default liveness)
+    bool def_map = (nmat == nl || nmat == 1);
+    for (int i1 = 0; def_map && i1 < 2 * nm; ++i1)
+        for (int l = 0; l < nl; ++l) {
+            const int want = ((i1 >> 1) <= l) ? (nmat == 1 ? 0 : l) : -1;
+            if (slot_map_h[i1 * nl + l] != want) { def_map = false; break; }
+        }
+    double fill = 0.0;
+    for (size_t i = 0; i < band.size() / 2; ++i) fill += band[2 * i + 1] - band[2 * i];
+    fill /= (double)(band.size() / 2) * nr;
+    const bool dense = def_map && !rotated && nterms > 0 && fill > 0.5 && nr % EG_K == 0 && (ncomp_out * nr) % EG_M == 0 &&
+                       !ell_no_gemm();
+    if (!dense) {                                     // the banded kernel stages all input lines of 8 slots in LDS
+        const size_t lds = (size_t)ncomp_in * nr * ELL_S * sizeof(double);
+        if (lds > 160 * 1024) return fail("ell_terms_create: too many components x radial modes for the LDS staging");
+        static size_t lds_opted = 64 * 1024;          // the attribute belongs to the kernel, not the handle: only raise
+                                                      // (one device and one creating thread per process, as everywhere here)
+        if (lds > lds_opted) {
+            DDH_HIP(hipFuncSetAttribute((const void *)ell_terms_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            DDH_HIP(hipFuncSetAttribute((const void *)ell_terms_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            lds_opted = lds;
         }
     }
-    if (check_hip(hipMalloc((void **)&p->d_meta, meta.size() * sizeof(int)), "hipMalloc") ||
+    std::vector<int> tmap((size_t)ncomp_out * ncomp_in, -1);
+    for (int t = 0; t < nterms; ++t) tmap[(size_t)co_h[t] * ncomp_in + ci_h[t]] = t;
+    EllTerms *p = new EllTerms();
+    p->kind = H_ELLT;
+    p->nm = nm; p->nl = nl; p->nr = nr; p->ncomp_out = ncomp_out; p->ncomp_in = ncomp_in; p->nterms = nterms; p->nmat = nmat;
+    p->dense = dense;
+    p->rotated = rotated;
+    if (check_hip(hipMalloc((void **)&p->d_tmap, tmap.size() * sizeof(int)), "hipMalloc") ||
+        check_hip(hipMemcpy(p->d_tmap, tmap.data(), tmap.size() * sizeof(int), hipMemcpyHostToDevice), "hipMemcpy") ||
+        check_hip(hipMalloc((void **)&p->d_meta, meta.size() * sizeof(int)), "hipMalloc") ||
         check_hip(hipMalloc((void **)&p->d_first, first.size() * sizeof(int)), "hipMalloc") ||
         check_hip(hipMalloc((void **)&p->d_mats, mb), "hipMalloc") ||
         check_hip(hipMalloc((void **)&p->d_slot, 2L * nm * nl * sizeof(int)), "hipMalloc") ||
@@ -529,8 +602,7 @@ int ddh_ell_terms_apply_acc(ddh_handle h, const double *x, double *y, int accumu
     EllTerms *p = (EllTerms *)lookup_handle(h, H_ELLT);
     if (!p) return -1;
     if (x == y) return fail("ell_terms_apply: in-place unsupported");
-    static const bool no_gemm = getenv("DDH_ELL_NO_GEMM") != nullptr;
-    if (p->dense && !no_gemm) {
+    if (p->dense) {
         const dim3 grid((unsigned)(p->ncomp_out * p->nr / EG_M), (unsigned)p->nl, (unsigned)((2 * p->nm + EG_N - 1) / EG_N));
         const size_t lds = (size_t)(EG_K * EG_LD > EG_N * EG_M ? EG_K * EG_LD : EG_N * EG_M) * sizeof(double);
         DDH_HIP(hipFuncSetAttribute((const void *)ell_gemm_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -542,13 +614,10 @@ int ddh_ell_terms_apply_acc(ddh_handle h, const double *x, double *y, int accumu
     if (accumulate) return fail("ell_terms_apply_acc: accumulation is implemented for the dense (GEMM) path only");
     const int T = p->nr >= 256 ? 256 : (p->nr > 64 ? 128 : 64);
     const dim3 grid((unsigned)((2 * p->nm + ELL_S - 1) / ELL_S), (unsigned)p->nl), block(T, ELL_CO);
-    const size_t lds = (size_t)p->ncomp_in * p->nr * ELL_S * sizeof(double);
-    if (lds > 64 * 1024) {
-        if (lds > 160 * 1024) return fail("ell_terms_apply: too many components x radial modes for the LDS staging");
-        DDH_HIP(hipFuncSetAttribute((const void *)ell_terms_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    }
-    hipLaunchKernelGGL(ell_terms_kernel, grid, block, lds, as_stream(stream), x, y, p->d_meta, p->d_first, p->d_slot,
-                       p->d_band, p->d_rows, p->d_mats, p->nm, p->nl, p->nr, p->nmat, p->ncomp_in, p->ncomp_out);
+    const size_t lds = (size_t)p->ncomp_in * p->nr * ELL_S * sizeof(double);      // checked and opted in to at creation
+    hipLaunchKernelGGL(p->rotated ? ell_terms_kernel<true> : ell_terms_kernel<false>, grid, block, lds, as_stream(stream), x, y,
+                       p->d_meta, p->d_first, p->d_slot, p->d_band, p->d_rows, p->d_mats, p->nm, p->nl, p->nr, p->nmat,
+                       p->ncomp_in, p->ncomp_out);
     DDH_HIP(hipGetLastError());
     return 0;
 }

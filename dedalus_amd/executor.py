@@ -476,10 +476,8 @@ class HipExecutor:
     def make_ell_terms(self, nm, nl, nr, ncomp_out, terms, slot_map=None, rot=None):
         """terms: list of (co, ci, mats [nmat][nr][nr]); slot_map [2 nm][nl] -> matrix index or -1 (default: ell where
         ell >= m) -> device radial operator (ddh_ell_terms_create).  rot: per term 0 / 1; a term with rot = 1 is i times
-        its matrix on cos + i msin (ddh_ell_terms_create_cx: the curl)."""
-        if rot is not None and any(rot):
-            return EllTermsCx(self, nm, nl, nr, ncomp_out, terms, slot_map, rot)
-        return EllTerms(self, nm, nl, nr, ncomp_out, terms, slot_map)
+        its matrix on cos + i msin (the curl)."""
+        return EllTerms(self, nm, nl, nr, ncomp_out, terms, slot_map, rot)
 
     def make_ell_mix(self, nm, nl, nr, ncomp_out, ncomp_in, terms, slot_map=None):
         """terms: list of (co, ci, q [nq]) with one real scalar per slot id; slot_map [2 nm][nl] -> row of q or -1 (default:
@@ -649,30 +647,44 @@ def default_slot_map(nm, nl):
 
 
 class EllTerms:
-    """Device term list.  With the default slot map, blocks that are mostly full (the per-ell LHS inverses between shell
-    variables) go to a second handle that runs as an FP64 MFMA GEMM and accumulates onto the banded part."""
+    """Device term list; rot: per term 0 / 1, a term with rot = 1 is i times its matrix (one streaming launch for the real
+    and the rotated terms).  With the default slot map and no rotated term, blocks that are mostly full (the per-ell LHS
+    inverses between shell variables) go to a second handle that runs as an FP64 MFMA GEMM and accumulates onto the
+    banded part."""
 
-    def __init__(self, ex, nm, nl, nr, ncomp_out, terms, slot_map=None, _split=True):
+    def __init__(self, ex, nm, nl, nr, ncomp_out, terms, slot_map=None, rot=None, _split=True):
         self.ex = ex
         self.dense_part = None
-        if _split and slot_map is None and nr % 64 == 0 and (ncomp_out * nr) % 64 == 0 and len(terms) > 1:
+        rot = [0] * len(terms) if rot is None else [int(r) for r in rot]
+        if len(rot) != len(terms):
+            raise ValueError("one rot flag per term")
+        if (_split and slot_map is None and not any(rot) and nr % 64 == 0 and (ncomp_out * nr) % 64 == 0
+                and len(terms) > 1):
             fill = [np.count_nonzero(t[2]) / t[2].size for t in terms]
             dense = [t for t, f in zip(terms, fill) if f > 0.5]
             sparse = [t for t, f in zip(terms, fill) if f <= 0.5]
             if dense and sparse:
                 self.dense_part = EllTerms(ex, nm, nl, nr, ncomp_out, dense, None, _split=False)
-                terms = sparse
-        terms = sorted(terms, key=lambda t: t[0])
+                terms, rot = sparse, [0] * len(sparse)
+        order = sorted(range(len(terms)), key=lambda i: terms[i][0])
+        terms, rot = [terms[i] for i in order], [rot[i] for i in order]
         co = np.ascontiguousarray([t[0] for t in terms], dtype=np.int32)
         ci = np.ascontiguousarray([t[1] for t in terms], dtype=np.int32)
+        rt = np.ascontiguousarray(rot, dtype=np.int32)
         nmat = int(terms[0][2].shape[0]) if terms else nl
         mats = np.zeros((max(len(terms), 1), nmat, nr, nr))
         for i, t in enumerate(terms):
             mats[i] = t[2]
         sm = np.ascontiguousarray(default_slot_map(nm, nl) if slot_map is None else slot_map, dtype=np.int32)
+        if sm.shape != (2 * nm, nl):
+            raise ValueError("slot map must be [2 nm][nl]")
+        self.shape_in = (int(ci.max()) + 1 if terms else 1, 2 * nm, nl, nr)
+        self.shape_out = (int(ncomp_out), 2 * nm, nl, nr)
+        self._tail = self.shape_in[1:]
         self.handle = C.c_uint64(0)
-        libhip.call("ddh_ell_terms_create", C.byref(self.handle), int(nm), int(nl), int(nr), int(ncomp_out), len(terms),
-                    libhip.as_ip(co), libhip.as_ip(ci), nmat, libhip.as_dp(mats), libhip.as_ip(sm))
+        libhip.call("ddh_ell_terms_create", C.byref(self.handle), int(nm), int(nl), int(nr), int(ncomp_out),
+                    self.shape_in[0], len(terms), libhip.as_ip(co), libhip.as_ip(ci), libhip.as_ip(rt), nmat,
+                    libhip.as_dp(mats), libhip.as_ip(sm))
         # algorithmic work of one application: every non-zero of A[mat] times the slots that use that matrix
         uses = np.bincount(sm[sm >= 0].ravel(), minlength=nmat)[:nmat] if nmat else np.zeros(0)
         nnz = np.count_nonzero(mats.reshape(mats.shape[0], nmat, -1), axis=2).sum(axis=0) if terms else np.zeros(nmat)
@@ -680,6 +692,13 @@ class EllTerms:
         self._mat_bytes = float(np.count_nonzero(mats)) * 8
 
     def apply(self, x, y):
+        xs = x.shape                                  # (torch.Size compares as a tuple: one pass, no copies)
+        if (xs[1:] != self._tail or xs[0] < self.shape_in[0] or y.shape != self.shape_out
+                or not (x.is_contiguous() and y.is_contiguous())):
+            if not (x.is_contiguous() and y.is_contiguous()):
+                raise ValueError("ell terms: contiguous operands only")
+            raise ValueError("ell terms: operand shapes %s -> %s do not match the term list (%s -> %s)"
+                             % (tuple(x.shape), tuple(y.shape), self.shape_in, self.shape_out))
         libhip.note_cost("ddh_ell_terms_apply", 2.0 * self._madds, self._mat_bytes + (x.numel() + y.numel()) * 8)
         libhip.call("ddh_ell_terms_apply", self.handle, ptr(x), ptr(y), self.ex.dev.stream)
         if self.dense_part is not None:
@@ -829,52 +848,6 @@ class BorderedBandInverse:
         libhip.call("ddh_ellband_bordered_inverse", ptr(self.x), self.n, self.j0, ptr(self.wM), ptr(self.wL), self.dM, self.dL,
                     float(a), float(b), ptr(self.out), self.ex.dev.stream)
         return self.out
-
-
-class EllTermsCx:
-    """Device term list with rotated (imaginary) terms: one streaming launch for the real and the rotated terms."""
-
-    def __init__(self, ex, nm, nl, nr, ncomp_out, terms, slot_map, rot):
-        self.ex = ex
-        if len(rot) != len(terms):
-            raise ValueError("one rot flag per term")
-        order = sorted(range(len(terms)), key=lambda i: terms[i][0])
-        terms, rot = [terms[i] for i in order], [int(rot[i]) for i in order]
-        co = np.ascontiguousarray([t[0] for t in terms], dtype=np.int32)
-        ci = np.ascontiguousarray([t[1] for t in terms], dtype=np.int32)
-        rt = np.ascontiguousarray(rot, dtype=np.int32)
-        nmat = int(terms[0][2].shape[0])
-        mats = np.zeros((len(terms), nmat, nr, nr))
-        for i, t in enumerate(terms):
-            mats[i] = t[2]
-        sm = np.ascontiguousarray(default_slot_map(nm, nl) if slot_map is None else slot_map, dtype=np.int32)
-        if sm.shape != (2 * nm, nl):
-            raise ValueError("slot map must be [2 nm][nl]")
-        self.shape_in = (int(ci.max()) + 1, 2 * nm, nl, nr)
-        self.shape_out = (ncomp_out, 2 * nm, nl, nr)
-        self.handle = C.c_uint64(0)
-        libhip.call("ddh_ell_terms_create_cx", C.byref(self.handle), int(nm), int(nl), int(nr), int(ncomp_out),
-                    self.shape_in[0], len(terms), libhip.as_ip(co), libhip.as_ip(ci), libhip.as_ip(rt), nmat,
-                    libhip.as_dp(mats), libhip.as_ip(sm))
-        uses = np.bincount(sm[sm >= 0].ravel(), minlength=nmat)[:nmat]
-        nnz = np.count_nonzero(mats.reshape(mats.shape[0], nmat, -1), axis=2).sum(axis=0)
-        self._madds = float(np.dot(nnz, uses))
-        self._mat_bytes = float(np.count_nonzero(mats)) * 8
-
-    def apply(self, x, y):
-        if tuple(x.shape)[1:] != self.shape_in[1:] or int(x.shape[0]) < self.shape_in[0] or tuple(y.shape) != self.shape_out:
-            raise ValueError("ell terms: operand shapes %s -> %s do not match the term list (%s -> %s)"
-                             % (tuple(x.shape), tuple(y.shape), self.shape_in, self.shape_out))
-        if not (x.is_contiguous() and y.is_contiguous()):
-            raise ValueError("ell terms: contiguous operands only")
-        libhip.note_cost("ddh_ell_terms_apply_cx", 2.0 * self._madds, self._mat_bytes + (x.numel() + y.numel()) * 8)
-        libhip.call("ddh_ell_terms_apply_cx", self.handle, ptr(x), ptr(y), self.ex.dev.stream)
-
-    def __del__(self):
-        try:
-            libhip.call("ddh_destroy", self.handle)
-        except Exception:
-            pass
 
 
 class EllMix:

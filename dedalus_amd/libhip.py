@@ -65,7 +65,7 @@ SIGNATURES = {
     "ddh_sphere_terms_apply": [_h, _vp, _vp, _vp],
     "ddh_cgemv_batch_create": [_hp, _i, _i, _i, _dp],
     "ddh_cgemv_batch_apply": [_h, _vp, _vp, _vp],
-    "ddh_ell_terms_create": [_hp, _i, _i, _i, _i, _i, _ip, _ip, _i, _dp, _ip],
+    "ddh_ell_terms_create": [_hp, _i, _i, _i, _i, _i, _i, _ip, _ip, _ip, _i, _dp, _ip],
     "ddh_ell_terms_apply": [_h, _vp, _vp, _vp],
     "ddh_dense_inverse_create": [_hp, _i, _ip, _i, _dp, _dp, C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte)],
     "ddh_dense_inverse_elements": [_h, C.POINTER(_l)],
@@ -76,8 +76,6 @@ SIGNATURES = {
     "ddh_ell_terms_prune": [_h, _vp],
     "ddh_ell_blocks_from_dense": [_vp, _vp, _i, _i, _i, _vp],
     "ddh_ell_terms_apply_acc": [_h, _vp, _vp, _i, _vp],
-    "ddh_ell_terms_create_cx": [_hp, _i, _i, _i, _i, _i, _i, _ip, _ip, _ip, _i, _dp, _ip],
-    "ddh_ell_terms_apply_cx": [_h, _vp, _vp, _vp],
     "ddh_ell_mix_create": [_hp, _i, _i, _i, _i, _i, _i, _ip, _ip, _i, _dp, _ip],
     "ddh_ell_mix_apply": [_h, _vp, _vp, _vp],
     "ddh_ellband_create": [_hp, _i, _i, _i, _i, _i, _i, _i, _l, _ip, _ip, _ip, C.POINTER(_l), C.POINTER(_l), _dp, _dp, _dp, _dp],

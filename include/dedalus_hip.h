@@ -215,25 +215,21 @@ int ddh_cgemv_batch_apply(ddh_handle h, const double *x, double *y, void *stream
  * radial matrices (nr x nr, row major in mats_h [nterms][nmat][nr][nr]) selected per slot by
  * id = slot_map_h[i1 * nl + ell] (-1: the slot carries no mode and is zeroed; normally id = ell).  Replaces
  * SphericalEllOperator.operate / subproblem_matrix (core/operators.py:3108-3222) and, with the per-ell LHS inverses
- * as matrices, the per-ell subproblem solves.  Terms sorted by co.                                              */
-int ddh_ell_terms_create(ddh_handle *h, int nm, int nl, int nr, int ncomp_out, int nterms, const int *co_h,
-                         const int *ci_h, int nmat, const double *mats_h, const int *slot_map_h);
+ * as matrices, the per-ell subproblem solves.  Terms sorted by co.  ncomp_in: components of x; nr <= 32767.
+ * rot_h (NULL: all 0) holds a flag per term.  rot_h[t] = 0: the term acts as above.  rot_h[t] = 1: the term is i A_t on
+ * the complex number cos + i msin of every azimuthal mode, y[co][2m + 0] += -A x[ci][2m + 1], y[co][2m + 1] += +A
+ * x[ci][2m + 0] -- the real-dtype branch of SphericalCurl.operate (core/operators.py:3944-3978) with the purely
+ * imaginary radial matrices of SphericalCurl._radial_matrix (:3889-3901); the same rotation as mult_1j in its
+ * subproblem_matrix (:3929).  A slot with slot_map_h < 0 is never read (not as the other part of its pair either) and
+ * receives +0.  Real and rotated terms of an output component are summed in one launch, in term order, without atomics.
+ * Lists of mostly full blocks with the default slot map, sizes that tile and no rotated term run as per-ell FP64 MFMA
+ * GEMMs; all others stream their banded matrices, and their ncomp_in * nr * 64 bytes of LDS must fit 160 KiB.        */
+int ddh_ell_terms_create(ddh_handle *h, int nm, int nl, int nr, int ncomp_out, int ncomp_in, int nterms, const int *co_h,
+                         const int *ci_h, const int *rot_h, int nmat, const double *mats_h, const int *slot_map_h);
 int ddh_ell_terms_apply(ddh_handle h, const double *x, double *y, void *stream);
 /* accumulate != 0: y += A x (dense term lists only: the FP64 MFMA per-ell GEMM path); used to apply a term list
  * split into its banded part (first, writes y) and its dense blocks (second, accumulates).              */
 int ddh_ell_terms_apply_acc(ddh_handle h, const double *x, double *y, int accumulate, void *stream);
-/* Term lists with imaginary terms (the curl of shell vector fields): as ddh_ell_terms_create, plus a flag per term.
- * rot_h[t] = 0: the term acts as above.  rot_h[t] = 1: the term is i A_t on the complex number cos + i msin of every
- * azimuthal mode, y[co][2m + 0] += -A x[ci][2m + 1], y[co][2m + 1] += +A x[ci][2m + 0] -- the real-dtype branch of
- * SphericalCurl.operate (core/operators.py:3944-3978) with the purely imaginary radial matrices of
- * SphericalCurl._radial_matrix (:3889-3901); the same rotation as mult_1j in its subproblem_matrix (:3929).  A slot
- * with slot_map_h < 0 is never read (not as the other part of its pair either) and receives +0.  Real and rotated
- * terms of an output component are summed in one launch, in term order, without atomics; banded matrices are
- * streamed (no GEMM path).  ncomp_in: components of x.  ncomp_in * nr * 64 bytes of LDS must fit 160 KiB.         */
-int ddh_ell_terms_create_cx(ddh_handle *h, int nm, int nl, int nr, int ncomp_out, int ncomp_in, int nterms,
-                            const int *co_h, const int *ci_h, const int *rot_h, int nmat, const double *mats_h,
-                            const int *slot_map_h);
-int ddh_ell_terms_apply_cx(ddh_handle h, const double *x, double *y, void *stream);
 /* Component mixes of shell tensor fields (transpose, radial and angular components): the identity along n, one real scalar
  * per term and slot id,  y[co][i1][ell][:] = sum_t q_h[t][id] x[ci_t][i1][ell][:],  id = slot_map_h[i1][ell] in [0, nq);
  * q_h is [nterms][nq], term-major (id: the ell of the slot, or one of the extra ids past nl for the slots that the packed

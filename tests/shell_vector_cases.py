@@ -1,11 +1,12 @@
 """Cases of the shell cross product and curl (tests/test_shell_vector_ops.py, tests/test_gpu_shell_vector_ops.py,
-tools/make_golden_shell_vector_ops.py -> tests/golden/shell_vector_ops.npz), and the kernel-level cases that pin
-ddh_ell_terms_apply_cx (csrc/ddh_ellcurl.hip) at the edges of its launch shape.
+tools/make_golden_shell_vector_ops.py -> tests/golden/shell_vector_ops.npz), and the kernel-level cases that pin the
+banded kernel of ddh_ell_terms_apply (csrc/ddh_sphere.hip, both instances) at the edges of its launch shape.
 
 Launch shape of the kernel: one workgroup = 8 consecutive (m, part) slots of one ell; 64 / 128 / 256 threads along the
 output radial index for nr <= 64 / <= 255 / >= 256; 4 output components at a time.  Hence the edges: 2 nm = 8 | 10,
 nr = 64 | 65 and 255 | 256, ncomp_out = 4 | 5 (the curl itself has 3), and ncomp_in * nr * 64 bytes of LDS on either side
-of 64 KiB, above which the launch opts in to a larger allocation: nr = 341 | 342 for three input components."""
+of 64 KiB, above which the creation opts in to a larger allocation: nr = 341 | 342 for three input components.  One case
+has the shape of the per-ell GEMM path (full matrices, sizes that tile it): its rotated terms keep it on the banded kernel."""
 import numpy as np
 
 RADII = (0.7, 1.9)
@@ -82,6 +83,7 @@ KERNEL_CASES = [
     ("nr342", 1, 2, 342, 3, 3, 2, ()),
     ("co4", 3, 4, 9, 4, 3, 9, ()),
     ("co5_mixed_ids", 3, 4, 9, 5, 2, 2, ((4, 3),)),
+    ("gemm_shaped", 4, 9, 64, 2, 3, 64, ()),
 ]
 
 

@@ -2,7 +2,8 @@
 
   * (a), (b) of tests/shell_vector_cases.py through the public d3 names against the reference's results
     (tests/golden/shell_vector_ops.npz), with the bounds of tests/test_shell_vector_ops.py;
-  * ddh_ell_terms_apply_cx pinned at the edges of its launch shape: a longdouble product of the same term list, entry by
+  * the banded kernel of ddh_ell_terms_apply pinned at the edges of its launch shape, the instance with rotated terms (the
+    flags as generated) and the one without (all flags zero): a longdouble product of the same term list, entry by
     entry within (K + 2) u sum |a| |x| (K: products summed for that entry; the form of tests/test_gpu_swsh_kernels.py),
     behind NaN guards around the output and NaN in every input slot that carries no mode -- the (m, ell) = (0, 0) msin
     slot among them: those slots receive +0, nothing outside the output changes, two calls give identical bits, a call
@@ -65,10 +66,14 @@ def guards_intact(ex, buf, n):
     return np.isnan(h[:GUARD]).all() and np.isnan(h[GUARD + n:]).all()
 
 
+@pytest.mark.parametrize("rot_form", ["as_generated", "all_zero"])
 @pytest.mark.parametrize("label", [c[0] for c in sv.KERNEL_CASES])
-def test_ell_terms_cx_kernel_pinned(ex, label):
+def test_ell_terms_kernel_pinned(ex, label, rot_form):
     import torch
     nm, nl, nr, nco, terms, rot, slot_map, x = sv.kernel_case(label)
+    if rot_form == "all_zero":
+        rot = [0] * len(rot)
+    assert any(rot) == (rot_form == "as_generated")
     ref, mag, cnt = sv.kernel_reference(nm, nl, nr, nco, terms, rot, slot_map, x)
     dev = ex.make_ell_terms(nm, nl, nr, nco, terms, slot_map, rot=rot)
     n = nco * 2 * nm * nl * nr
