@@ -337,10 +337,13 @@ class SurfaceBasis:
         return self.shell.recombination_matrix(rank, forward)
 
     def __eq__(self, other):
-        return isinstance(other, SurfaceBasis) and other.shell is self.shell and other.radius == self.radius
+        # the sphere r = R of a shell and of its derivative bases (k + 1, ...) is one basis, as in the reference, whose
+        # S2 basis does not know k: radial(grad(A)(r=R)) + SphericalEllProduct(A, ...)(r=R) is a sum on one surface
+        root = lambda b: getattr(b.shell, "_root", b.shell)
+        return isinstance(other, SurfaceBasis) and root(other) is root(self) and other.radius == self.radius
 
     def __hash__(self):
-        return hash((id(self.shell), self.radius))
+        return hash((id(getattr(self.shell, "_root", self.shell)), self.radius))
 
 
 def _radial_gemm(dist, basis, scale, nc, forward_dir):
@@ -1715,6 +1718,132 @@ def angular(a, index=0):
 transpose, TransposeComponents, RadialComponent, AngularComponent = trans, trans, radial, angular
 
 
+class ShEllProduct(ShOperand):
+    """SphericalEllProduct(T, coordsys, ell_func) of a shell (volume) operand (SphericalEllProductField, core/operators.py:
+    4169-4214): every regularity component times ell_func(ell + regtotal), the identity along n, no mixing between
+    components; basis, rank and sig are those of the operand.  A diagonal EllMixList.  `parts` is a list of
+    (factor, ell_func): scalar multiples and sums of ell products of one operand stay one node and one mix.
+    ell_func is called on the host, once per distinct ell + regtotal of an existing mode, when the node is made."""
+
+    name = "SphericalEllProduct"
+
+    def __init__(self, arg, coordsys, ell_func, _parts=None):
+        name = self.name
+        if not isinstance(arg, ShOperand):
+            raise ValueError("%s needs a field operand" % name)
+        if coordsys is not arg.dist.coordsys:
+            raise ValueError("%s: %r is not the operand's coordinate system" % (name, coordsys))
+        if isinstance(arg, RadialField):
+            raise NotImplementedError("%s of a radial operand %r" % (name, arg))
+        if isinstance(arg, ConstField) or arg.basis is None:
+            raise NotImplementedError("%s of a constant operand %r" % (name, arg))
+        if isinstance(arg, ShReduced):
+            raise NotImplementedError("%s of a reduced operand (%s)" % (name, arg.what))
+        _no_s2_index(name, arg)
+        if isinstance(arg.basis, SurfaceBasis):
+            # the reference dispatches to SphericalEllProductField alone, whose radial matrices need the operand's radial
+            # basis: a surface operand (u(r=R0)) fails there.  Take the product first: SphericalEllProduct(u, ...)(r=R0)
+            raise NotImplementedError("%s of the surface operand %r: multiply in the volume, then interpolate" % (name, arg))
+        parts = [(1.0, ell_func)] if _parts is None else list(_parts)
+        if not all(callable(f) for (a, f) in parts):
+            raise ValueError("%s needs a function of ell" % name)
+        self.arg, self.args, self.coordsys, self.parts = arg, (arg,), coordsys, parts
+        self.dist, self.basis, self.rank, self._sig = arg.dist, arg.basis, arg.rank, arg.sig
+        self.q = self._table()
+        self._dev = None
+
+    def _table(self):
+        """q [ncomp][nl]: sum of factor * ell_func(ell + regtotal) on the modes that exist, 0 elsewhere"""
+        nl = self.basis.sphere.nl
+        idx = reg_indices(self.rank)
+        q = np.zeros((len(idx), nl))
+        for a, func in self.parts:
+            seen = {}
+            for c, t in enumerate(idx):
+                rt = regtotal(t)
+                for ell in range(nl):
+                    if not regularity_allowed(ell, t):
+                        continue                                  # no mode: ell_func is not asked, the entry stays 0
+                    if ell + rt not in seen:
+                        v = func(ell + rt)
+                        if isinstance(v, numbers.Complex) and not isinstance(v, numbers.Real) or np.iscomplexobj(v):
+                            raise NotImplementedError("%s: ell_func(%d) = %r is complex; the per-ell systems are real"
+                                                      % (self.name, ell + rt, v))
+                        v = float(v)
+                        if not np.isfinite(v):
+                            raise ValueError("%s: ell_func(%d) = %r is not finite" % (self.name, ell + rt, v))
+                        seen[ell + rt] = v
+                    q[c, ell] += a * seen[ell + rt]
+        return q
+
+    def _like(self, parts):
+        return ShEllProduct(self.arg, self.coordsys, None, _parts=parts)
+
+    def __mul__(self, other):
+        if isinstance(other, numbers.Number):
+            return self._like([(float(other) * a, f) for (a, f) in self.parts])
+        return ShOperand.__mul__(self, other)
+
+    __rmul__ = __mul__
+
+    def __neg__(self):
+        return self * -1.0
+
+    def __truediv__(self, other):
+        if isinstance(other, numbers.Number):
+            return self * (1.0 / other)
+        return NotImplemented
+
+    def __add__(self, other):
+        if isinstance(other, ShEllProduct) and other.arg is self.arg:
+            return self._like(self.parts + other.parts)
+        return ShOperand.__add__(self, other)
+
+    __radd__ = __add__
+
+    def __sub__(self, other):
+        if isinstance(other, ShEllProduct) and other.arg is self.arg:
+            return self + (-other)
+        return ShOperand.__sub__(self, other)
+
+    def mixlist(self):
+        """per ell (the subproblem matrices of a left-hand side)"""
+        return EllMixList(self.ncomp, self.ncomp, [(c, c, self.q[c]) for c in range(self.ncomp) if np.any(self.q[c] != 0)])
+
+    def _slot_mix(self):
+        """(terms (c, c, q [nq]), slot map [2 nml][nl]) for EVALUATION: SphericalEllOperator.operate (core/operators.py:
+        3136-3167) loops over the ell_maps boxes and accumulates, so a slot that the packed layout covers with several
+        boxes gets the sum of their scalars (the extra ids of operate_slot_sequences, as for the radial operators)."""
+        sb = self.basis.sphere
+        seqs, slot = operate_slot_sequences(sb)
+        terms = [(c, c, np.concatenate([q, [sum(q[l] for l in seq) for seq in seqs]])) for (c, _, q) in self.mixlist().terms]
+        return terms, np.ascontiguousarray(slot[2 * sb.m0:2 * (sb.m0 + sb.nml)])
+
+    def eval_c(self):
+        ex = self.dist.executor
+        sb = self.basis.sphere
+        if getattr(ex, "make_ell_mix", None) is None:
+            raise NotImplementedError("the executor %r has no component mix (make_ell_mix)" % (ex,))
+        if self._dev is None or self._dev[0] is not ex:
+            terms, slot_map = self._slot_mix()
+            self._dev = (ex, ex.make_ell_mix(sb.nml, sb.nl, self.basis.Nr, self.ncomp, self.ncomp, terms, slot_map))
+        y = ex.empty((self.ncomp, 2 * sb.nml, sb.nl, self.basis.Nr))
+        self._dev[1].apply(self.arg.eval_c(), y)
+        return y
+
+    def lin(self, variables):
+        d, isdt = self.arg.lin(variables)
+        ml = self.mixlist()
+        return {i: ml.compose(t) for i, t in d.items()}, isdt
+
+
+def SphericalEllProduct(a, coordsys, ell_func):
+    """d3.SphericalEllProduct of a shell operand; a number gives 0 as in the reference's dispatch (core/operators.py:4160-4163)"""
+    if isinstance(a, numbers.Number):
+        return 0
+    return ShEllProduct(a, coordsys, ell_func)
+
+
 def dt(a):
     return ShDt(a)
 
@@ -2015,7 +2144,7 @@ class ShellProblem(CurvilinearProblem):
                      Laplacian=lap, Gradient=grad, Divergence=div, TimeDerivative=dt, Trace=trace,
                      Integrate=integ, ave=ave, Average=ave, curl=curl, Curl=curl, cross=cross, CrossProduct=cross,
                      trans=trans, transpose=trans, TransposeComponents=trans, radial=radial, RadialComponent=radial,
-                     angular=angular, AngularComponent=angular)
+                     angular=angular, AngularComponent=angular, SphericalEllProduct=SphericalEllProduct)
 
     def __init__(self, variables, namespace=None, time="t"):
         super().__init__(variables, namespace, time)

@@ -65,6 +65,13 @@ def _no_components(name):
 
 radial = RadialComponent = _dispatch("radial", _no_components("radial"))
 angular = AngularComponent = _dispatch("angular", _no_components("angular"))
+
+
+def _no_ell_product(operand, *args, **kw):
+    raise NotImplementedError("SphericalEllProduct of %r: defined for shell operands" % (operand,))
+
+
+SphericalEllProduct = _dispatch("SphericalEllProduct", _no_ell_product)
 MulCosine = _sphere.MulCosine
 _CartesianIVP, _CartesianLBVP = IVP, LBVP
 
