@@ -26,6 +26,10 @@ import numpy as np
 from scipy import sparse
 
 
+def _has_imag(v):
+    return v.dtype.kind == "c" and bool(np.any(v.imag != 0))
+
+
 class EllBandPlan:
     """Attributes (nl groups, nmax = largest system, all arrays padded):
         n[g]               system size (0: no valid modes, or a dense group)
@@ -36,7 +40,14 @@ class EllBandPlan:
         T[g]               (nbc, nbc) combination of the boundary rows (identity where there are none)
         P[g][i][s]         P_perm[i, i + 1 + s], s < mp
         MB, LB[g][i][d]    permuted, recombined M / L: entry (i, i - kl + d), d < kl + ku + 1
+        cx                 some banded group has a non-zero imaginary part (a curl on the left-hand side: i A on the
+                           complex number cos + i msin of an azimuthal mode, reference core/operators.py:3903-3942).
+                           MB / LB are then complex128 and the systems act on (cos, msin) slot pairs; T and P stay
+                           real, so a group whose boundary rows are complex goes to the dense path.  Without an
+                           imaginary part anywhere the plan is what it was: float64, byte for byte.
     """
+
+    cw_max = 64                # kl + ku of the widest complex window the device compiles (csrc/ddh_ellband.hip)
 
     def __init__(self, M_of, L_of, row_valid, col_valid, packed_rows, packed_cols, Nr, groups, kl_max=32, w_max=96,
                  cutoff=1e-12):
@@ -66,7 +77,20 @@ class EllBandPlan:
                 self.why_dense[g] = "band much wider than the median (kl %d, ku %d)" % (per[g]["kl"], per[g]["ku"])
                 self.dense_groups.append(g)
                 del per[g]
-            self.dense_groups.sort()
+        # The handle is created with the plan-wide max kl and max ku: these, not each group's own widths, have to fit the
+        # compiled windows (kl + ku <= 96, complex: 64).  The widest groups go dense until they do.
+        imag = {g: _has_imag(r["Mp"][2]) or _has_imag(r["Lp"][2]) for g, r in per.items()}
+        while per:
+            self.cx = any(imag[g] for g in per)
+            limit, what = (self.cw_max, "complex windows") if self.cx else (self.w_max, "windows")
+            if max(r["kl"] for r in per.values()) + max(r["ku"] for r in per.values()) <= limit:
+                break
+            g = max(per, key=lambda g: (per[g]["kl"] + per[g]["ku"], per[g]["ku"], g))
+            self.why_dense[g] = "band too wide for the %s beside the other groups (kl %d, ku %d)" % (what, per[g]["kl"], per[g]["ku"])
+            self.dense_groups.append(g)
+            del per[g]
+        self.cx = any(imag[g] for g in per)
+        self.dense_groups.sort()
         self.per = per
         self._rec_cache = None
         self.n = np.zeros(self.nl, dtype=np.int32)
@@ -84,8 +108,8 @@ class EllBandPlan:
         self.T = np.zeros((nl, max(self.nbc, 1), max(self.nbc, 1)))
         self.nbc_of = np.zeros(nl, dtype=np.int32)
         self.P = np.zeros((nl, nmax, max(self.mp, 1)))
-        self.MB = np.zeros((nl, nmax, W))
-        self.LB = np.zeros((nl, nmax, W))
+        self.MB = np.zeros((nl, nmax, W), dtype=np.complex128 if self.cx else np.float64)
+        self.LB = np.zeros((nl, nmax, W), dtype=np.complex128 if self.cx else np.float64)
         for g, r in per.items():
             n = r["n"]
             self.n[g] = n
@@ -96,7 +120,7 @@ class EllBandPlan:
             self.T[g, :k, :k] = r["T"]
             for name, dst in (("Mp", self.MB), ("Lp", self.LB)):
                 i, j, v = r[name]
-                dst[g, i, j - i + self.kl] = v
+                dst[g, i, j - i + self.kl] = v if self.cx else v.real
             i, j, v = r["Pp"]
             self.P[g, i, j - i - 1] = v
 
@@ -110,6 +134,9 @@ class EllBandPlan:
         # (dense or scipy.sparse matrices of the full (component, n) index space; sparse from here on)
         Ms = sparse.csr_matrix(M)[ridx][:, cidx].tocsr()
         Ls = sparse.csr_matrix(L)[ridx][:, cidx].tocsr()
+        if Ms.dtype.kind == "c" or Ls.dtype.kind == "c":
+            if Ms.imag.count_nonzero() == 0 and Ls.imag.count_nonzero() == 0:
+                Ms, Ls = Ms.real.tocsr(), Ls.real.tocsr()              # (no rotated term reaches this group)
         rcomp, rn, ccomp, cn = ridx // Nr, ridx % Nr, cidx // Nr, cidx % Nr
         bc = np.flatnonzero(np.isin(rcomp, packed_rows))
         tau = np.flatnonzero(np.isin(ccomp, packed_cols))
@@ -118,6 +145,10 @@ class EllBandPlan:
         if len(bc) and Ms[bc].count_nonzero():
             return "boundary rows with time derivatives"
         Rb = Ls[bc].toarray() if len(bc) else np.zeros((0, n))
+        if Rb.dtype.kind == "c":
+            if np.any(Rb.imag != 0):
+                return "complex boundary rows"                          # (T and P are real)
+            Rb = np.ascontiguousarray(Rb.real)
         if np.any(Rb[:, tau] != 0):
             return "boundary rows touch tau columns"
         # components coupled by boundary rows -> groups of variables that are recombined together
@@ -242,23 +273,26 @@ class EllBandPlan:
         n, kl, ku = int(self.n[g]), self.kl, self.ku
         W = kl + ku + 1
         A = a * self.MB[g, :n] + b * self.LB[g, :n]                    # [i][d] = entry (i, i - kl + d)
-        ab = np.zeros((2 * kl + ku + 1, n))
+        cx = getattr(self, "cx", False)                                # (complex: rhs_flat holds cos + i msin per column)
+        dt = complex if cx else float
+        gbtrf, gbtrs = (lapack.zgbtrf, lapack.zgbtrs) if cx else (lapack.dgbtrf, lapack.dgbtrs)
+        ab = np.zeros((2 * kl + ku + 1, n), dtype=dt)
         for d in range(W):
             i = np.arange(n)
             j = i - kl + d
             ok = (j >= 0) & (j < n)
             ab[kl + ku + i[ok] - j[ok], j[ok]] = A[i[ok], d]
-        lu, piv, info = lapack.dgbtrf(ab, kl, ku)
+        lu, piv, info = gbtrf(ab, kl, ku)
         if info:
             raise np.linalg.LinAlgError("gbtrf info %d" % info)
-        r = rhs_flat[self.row_index[g, :n]].astype(float)
+        r = rhs_flat[self.row_index[g, :n]].astype(dt)
         k = int(self.nbc_of[g])
         r[:k] = self.T[g, :k, :k] @ r[:k]
-        y, info = lapack.dgbtrs(lu, kl, ku, r, piv)
+        y, info = gbtrs(lu, kl, ku, r, piv)
         z = y.copy()
         for s in range(min(self.mp, n - 1)):                           # (a system shorter than the band of P has fewer)
             z[:n - 1 - s] += self.P[g, :n - 1 - s, s, None] * y[1 + s:]
-        out = np.zeros_like(rhs_flat, dtype=float)
+        out = np.zeros_like(rhs_flat, dtype=dt)
         out[self.col_index[g, :n]] = z
         return out
 
@@ -285,4 +319,4 @@ class BandBlockPlan:
         self.MB[0, i, j - i + self.kl] = M[i, j]
         self.LB[0, i, j - i + self.kl] = L[i, j]
         self.row_index = self.col_index = None           # (the caller gives element offsets directly)
-        self.per, self.dense_groups = {0: None}, []
+        self.per, self.dense_groups, self.cx = {0: None}, [], False

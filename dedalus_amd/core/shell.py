@@ -2153,7 +2153,9 @@ class ShellProblem(CurvilinearProblem):
 
     def _lin(self, node):
         d, isdt = node.lin(self.variables)
-        if any(t.rotated for t in d.values()):
+        # a rotated term (the curl: i A on cos + i msin) makes the per-ell systems complex: only where the executor
+        # solves such systems (csrc/ddh_ellband.hip, complex instances)
+        if any(t.rotated for t in d.values()) and not getattr(self.dist.executor, "complex_ell_systems", False):
             raise NotImplementedError("curl in a shell LHS: per-ell systems are real")
         return d, isdt
 
@@ -2236,7 +2238,10 @@ class ShellSolverBase:
         self.M_tl = self._system_termlist("M")
         self.L_tl = self._system_termlist("L")
         self.pack = _EllPack()
-        mk = lambda tl: self.ex.make_ell_terms(self.nm, self.nl, self.Nr, self.R, tl.terms)
+        self.cx = self.M_tl.rotated or self.L_tl.rotated          # complex per-ell systems on (cos, msin) pairs
+        self._assert_real_ell0()
+        mk = lambda tl: self.ex.make_ell_terms(self.nm, self.nl, self.Nr, self.R, tl.terms,
+                                               **(dict(rot=tl.rot) if tl.rotated else {}))
         self.M_id = self.pack.add(_Reshaped(self, mk(self.M_tl)))
         self.L_id = self.pack.add(_Reshaped(self, mk(self.L_tl)))
         self.X = self.ex.zeros((self.R, self.nx, self.ny))
@@ -2271,35 +2276,51 @@ class ShellSolverBase:
         return valid
 
     def _system_termlist(self, which):
+        """real blocks and rotated blocks (i A on cos + i msin: a curl) of one (co, ci) are kept apart"""
         blocks = {}
         Nr = self.Nr
         for eq, em in zip(self.problem.equations, self.emap):
             for i, t in eq[which].items():
                 vm = self.vmap[i]
-                for (co, ci, m) in t.terms:
+                for (co, ci, m), r in zip(t.terms, t.rot):
                     (so, oo, nro), (si, oi, nri) = em[co], vm[ci]
-                    blk = blocks.setdefault((so, si), np.zeros((self.nl, Nr, Nr)))
+                    blk = blocks.setdefault((r, so, si), np.zeros((self.nl, Nr, Nr)))
                     blk[:, oo:oo + nro, oi:oi + nri] += m[:, :nro, :nri]
-        out = []
-        for (co, ci), m in sorted(blocks.items()):
+        out, rot = [], []
+        for (r, co, ci), m in sorted(blocks.items()):
             m = m * self.row_valid[co][:, :, None] * self.col_valid[ci][:, None, :]
             m[np.abs(m) < 1e-12] = 0.0          # entry_cutoff of the reference's subproblem matrices (core/subsystems.py:536)
             if np.any(m != 0):
                 out.append((co, ci, m))
-        return EllTermList(self.R, self.R, out)
+                rot.append(r)
+        return EllTermList(self.R, self.R, out, rot)
 
     def _dense(self, tl, ell):
-        A = np.zeros((self.R * self.Nr, self.R * self.Nr))
-        for (co, ci, m) in tl.terms:
-            A[co * self.Nr:(co + 1) * self.Nr, ci * self.Nr:(ci + 1) * self.Nr] += m[ell]
+        """A_r + i A_i where the list has rotated terms, a float64 matrix where it has none"""
+        A = np.zeros((self.R * self.Nr, self.R * self.Nr), dtype=np.complex128 if tl.rotated else np.float64)
+        for (co, ci, m), r in zip(tl.terms, tl.rot):
+            A[co * self.Nr:(co + 1) * self.Nr, ci * self.Nr:(ci + 1) * self.Nr] += (1j * m[ell]) if r else m[ell]
         return A
+
+    def _assert_real_ell0(self):
+        """The curl's blocks vanish at ell = 0 (a vector has no 0 regularity component there), so the only validity hole
+        of the real storage, (m, ell, part) = (0, 0, 1) (reference core/basis.py:4299-4305), stays where it is and every
+        ell >= 1 system has both parts of every variable: the complex systems are exactly the reference's real-form ones."""
+        for which, tl in (("M", self.M_tl), ("L", self.L_tl)):
+            for (co, ci, m), r in zip(tl.terms, tl.rot):
+                if r and np.any(m[0] != 0):
+                    k = [i for i, em in enumerate(self.emap) if any(sc == co for (sc, off, nr) in em)][0]
+                    raise ValueError("equation %d (%s): the ell = 0 system has an imaginary part in %s"
+                                     % (k, self.problem.equations[k].get("string") or "no string", which))
 
     _dinv = None
 
     def _inverse_terms(self, a, b, old=None):
         """Per-ell inverse of (a M + b L) on the valid modes, formed and inverted on the device
         (executor.make_dense_inverse: M_ell and L_ell are uploaded once; a change of the timestep costs no host work),
-        then applied as a term list of dense blocks."""
+        then applied as a term list of dense blocks.  Complex systems (self.cx): the inverse B_r + i B_i is downloaded and a
+        new term list of real plus rotated blocks is built at every call -- a device-to-host copy per change of the timestep
+        on this path (LBVP once; IVP only with DDH_SHELL_DENSE=1, the band path keeps everything on the device)."""
         if self._dinv is None:
             ells = range(self.nl)
             Ms = [self._dense(self.M_tl, ell) for ell in ells]
@@ -2310,8 +2331,10 @@ class ShellSolverBase:
             for ell, (rv, cv) in enumerate(zip(rvs, cvs)):
                 if rv.sum() != cv.sum():
                     raise ValueError("ell = %d: %d valid equation modes for %d valid variable modes" % (ell, rv.sum(), cv.sum()))
-            self._dinv = self.ex.make_dense_inverse(Ms, Ls, rvs, cvs, complex_=False)
+            self._dinv = self.ex.make_dense_inverse(Ms, Ls, rvs, cvs, complex_=self.cx)
         flat = self._dinv.compute(a, b)
+        if self.cx:                        # B_r + i B_i: real blocks plus rotated blocks, one term list
+            return _Reshaped(self, self.ex.make_ell_terms_from_dense(self.nm, self.nl, self.Nr, self.R, flat, complex_=True))
         inner = old.dev if isinstance(old, _Reshaped) else None
         return _Reshaped(self, self.ex.make_ell_terms_from_dense(self.nm, self.nl, self.Nr, self.R, flat, old=inner))
 
@@ -2462,7 +2485,7 @@ class ShellInitialValueSolver(LUSlotSolver, ShellSolverBase):
                         dinv = self.ex.make_dense_inverse([self._dense(self.M_tl, g) for g in gs],
                                                           [self._dense(self.L_tl, g) for g in gs],
                                                           [self.row_valid[:, g, :].reshape(-1) for g in gs],
-                                                          [self.col_valid[:, g, :].reshape(-1) for g in gs], complex_=False)
+                                                          [self.col_valid[:, g, :].reshape(-1) for g in gs], complex_=self.cx)
                     self._band = dict(plan=plan, dev=dev, dinv=dinv)
                     logger.info("shell LHS: band LU for %d of %d ell (kl %d, ku %d); dense inverse for ell in %s" % (
                         len(plan.per), len(ells), plan.kl, plan.ku, plan.dense_groups))
@@ -2494,6 +2517,10 @@ class ShellInitialValueSolver(LUSlotSolver, ShellSolverBase):
                 shape = (self.R, 2 * self.nm, self.nl, self.Nr)
                 n2 = (self.R * self.Nr) ** 2
                 for k, g in enumerate(band["plan"].dense_groups):
+                    if self.cx:
+                        self.ex.dense_group_solve(inv["dense"][2 * k * n2:2 * (k + 1) * n2], rhs.reshape(shape),
+                                                  x.reshape(shape), g, complex_=True)
+                        continue
                     self.ex.dense_group_solve(inv["dense"][k * n2:(k + 1) * n2], rhs.reshape(shape), x.reshape(shape), g)
         else:
             inv.apply(rhs, x)

@@ -16,6 +16,7 @@ from .pencilpack import PencilPack
 class HipExecutor:
     name = "hip"
     mmt_pairs = True            # grouped transforms accept paired right-hand sides (ddh_grouped_mmt_set_pairs)
+    complex_ell_systems = True  # per-ell LHS systems may be complex: a curl on a shell left-hand side (EllBand, cx)
 
     def __init__(self, device=None):
         self.dev = device or Device.get()
@@ -511,9 +512,17 @@ class HipExecutor:
                     int(nslots), self.dev.stream)
         return self._cinv_out
 
-    def dense_group_solve(self, inv, rhs4, x4, g):
-        """x4[:, :, g, :] = inv @ rhs4[:, :, g, :] for one group kept on the dense path (inv: (ncomp nr)^2, device)"""
+    def dense_group_solve(self, inv, rhs4, x4, g, complex_=False):
+        """x4[:, :, g, :] = inv @ rhs4[:, :, g, :] for one group kept on the dense path (inv: (ncomp nr)^2, device).
+        complex_: inv holds interleaved complex entries and slots (2j, 2j + 1) are (re, im) of column j."""
         R, S, _, nr = rhs4.shape
+        if complex_:
+            t = self.torch
+            v = rhs4[:, :, g, :].reshape(R, S // 2, 2, nr).permute(0, 3, 1, 2).reshape(R * nr, S // 2, 2).contiguous()
+            A = t.view_as_complex(inv.reshape(R * nr, R * nr, 2))
+            y = t.view_as_real(A @ t.view_as_complex(v))                       # (R nr, S / 2, 2)
+            x4[:, :, g, :] = y.reshape(R, nr, S // 2, 2).permute(0, 2, 3, 1).reshape(R, S, nr)
+            return
         v = rhs4[:, :, g, :].permute(0, 2, 1).reshape(R * nr, S)
         x4[:, :, g, :] = (inv.reshape(R * nr, R * nr) @ v).reshape(R, nr, S).permute(0, 2, 1)
 
@@ -529,9 +538,22 @@ class HipExecutor:
         batch.nbytes = int(flat.numel()) * 8
         return batch
 
-    def make_ell_terms_from_dense(self, nm, nl, nr, ncomp, flat, old=None):
+    def make_ell_terms_from_dense(self, nm, nl, nr, ncomp, flat, old=None, complex_=False):
         """Term list of the per-ell dense blocks of `flat` = [nl][ncomp nr][ncomp nr] (device): the per-ell LHS inverses.
-        Sizes that tile the FP64 MFMA GEMM stay on the device end to end (old: a handle of the same shape to refill)."""
+        Sizes that tile the FP64 MFMA GEMM stay on the device end to end (old: a handle of the same shape to refill).
+        complex_: flat holds interleaved complex entries B_r + i B_i; the term list is the real blocks plus the rotated
+        blocks (i B_i on cos + i msin), one streaming launch."""
+        if complex_:
+            inv = self.download(flat).reshape(nl, ncomp * nr, ncomp * nr, 2)
+            blocks, rot = [], []
+            for part in (0, 1):
+                for co in range(ncomp):
+                    for ci in range(ncomp):
+                        blk = inv[:, co * nr:(co + 1) * nr, ci * nr:(ci + 1) * nr, part]
+                        if np.any(blk != 0):
+                            blocks.append((co, ci, np.ascontiguousarray(blk)))
+                            rot.append(part)
+            return self.make_ell_terms(nm, nl, nr, ncomp, blocks, rot=rot)
         if nr % 64 == 0 and (ncomp * nr) % 64 == 0:
             terms = old if isinstance(old, DenseEllTerms) else DenseEllTerms(self, nm, nl, nr, ncomp)
             terms.fill(flat)
@@ -772,16 +794,23 @@ class EllBand:
         c = lambda a, dt: np.ascontiguousarray(a, dtype=dt)
         self.handle = C.c_uint64(0)
         lp = lambda a: a.ctypes.data_as(C.POINTER(C.c_long))
-        libhip.call("ddh_ellband_create", C.byref(self.handle), int(nl), int(plan.nmax), int(plan.kl), int(plan.ku),
+        # a complex plan (a curl on the left-hand side): interleaved complex bands, slot pairs (2j, 2j + 1) = (re, im)
+        self.cx = bool(getattr(plan, "cx", False))
+        band = (lambda a: c(a, np.complex128).view(np.float64)) if self.cx else (lambda a: c(a, np.float64))
+        libhip.call("ddh_ellband_create_complex" if self.cx else "ddh_ellband_create", C.byref(self.handle), int(nl),
+                    int(plan.nmax), int(plan.kl), int(plan.ku),
                     int(plan.mp), int(plan.nbc), int(nslots), int(slot_stride), libhip.as_ip(c(plan.n, np.int32)),
                     libhip.as_ip(c(plan.nbc_of, np.int32)), libhip.as_ip(c(slot_limit, np.int32)), lp(rowoff), lp(coloff),
                     libhip.as_dp(c(plan.T, np.float64)), libhip.as_dp(c(plan.P, np.float64)),
-                    libhip.as_dp(c(plan.MB, np.float64)), libhip.as_dp(c(plan.LB, np.float64)))
+                    libhip.as_dp(band(plan.MB)), libhip.as_dp(band(plan.LB)))
         self.count = 0
-        # algorithmic cost of one solve (every (group, slot) column that can hold modes)
+        # algorithmic cost of one solve (every (group, slot) column that can hold modes).  Complex: per PAIR column 4x the
+        # real multiply-adds of the LU rows and 2x those of the real recombination, i.e. per slot 2x / 1x; the factor rows
+        # are twice the bytes, the right-hand side and the solution the same.
         cols = float(np.dot(plan.n.astype(np.float64), np.minimum(np.asarray(slot_limit), nslots)))
-        self._flops = 2.0 * (2 * plan.kl + plan.ku + plan.mp) * cols
-        self._bytes = 16.0 * cols + float(plan.n.sum()) * 8 * (2 * plan.kl + plan.ku + 1 + plan.mp)
+        k = 2 if self.cx else 1
+        self._flops = 2.0 * (k * (2 * plan.kl + plan.ku) + plan.mp) * cols
+        self._bytes = 16.0 * cols + float(plan.n.sum()) * 8 * (k * (2 * plan.kl + plan.ku + 1) + plan.mp)
 
     def factor(self, a, b, index=None):
         """-> index of the factorization (index: one to overwrite)"""

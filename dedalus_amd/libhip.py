@@ -79,6 +79,7 @@ SIGNATURES = {
     "ddh_ell_mix_create": [_hp, _i, _i, _i, _i, _i, _i, _ip, _ip, _i, _dp, _ip],
     "ddh_ell_mix_apply": [_h, _vp, _vp, _vp],
     "ddh_ellband_create": [_hp, _i, _i, _i, _i, _i, _i, _i, _l, _ip, _ip, _ip, C.POINTER(_l), C.POINTER(_l), _dp, _dp, _dp, _dp],
+    "ddh_ellband_create_complex": [_hp, _i, _i, _i, _i, _i, _i, _i, _l, _ip, _ip, _ip, C.POINTER(_l), C.POINTER(_l), _dp, _dp, _dp, _dp],
     "ddh_ellband_factor": [_h, _i, _d, _d, _ip, _vp],
     "ddh_ellband_solve": [_h, _i, _vp, _vp, _vp],
     "ddh_ellband_info": [_h, _ip, _ip, C.POINTER(_l)],

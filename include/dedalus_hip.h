@@ -284,6 +284,17 @@ int ddh_ellband_create(ddh_handle *h, int nl, int nmax, int kl, int ku, int mp, 
                        const int *n_h, const int *nbc_h, const int *slot_limit_h, const long *rowoff_h,
                        const long *coloff_h, const double *T_h, const double *P_h, const double *MB_h,
                        const double *LB_h);
+/* The same with COMPLEX matrices: MB_h / LB_h [nl][nmax][kl + ku + 1][2] interleaved (re, im); T_h and P_h stay real.  The
+ * curl of a shell field on a left-hand side is i A on the complex number cos + i msin of every azimuthal mode (the
+ * reference's SphericalCurl.subproblem_matrix, real-dtype branch with mult_1j, core/operators.py:3903-3942), so the
+ * system the reference factors per subproblem (libraries/matsolvers.py:129-160) is one complex band matrix per ell
+ * acting on slot pairs: slots (2j, 2j + 1) of the real system vectors are (re, im) of right-hand side j.  nslots and
+ * every slot_limit_h[g] must be even; compiled windows: kl <= 35, kl + ku <= 64.  factor / solve / info / ddh_destroy
+ * take either kind of handle. */
+int ddh_ellband_create_complex(ddh_handle *h, int nl, int nmax, int kl, int ku, int mp, int nbc, int nslots,
+                               long slot_stride, const int *n_h, const int *nbc_h, const int *slot_limit_h,
+                               const long *rowoff_h, const long *coloff_h, const double *T_h, const double *P_h,
+                               const double *MB_h, const double *LB_h);
 int ddh_ellband_factor(ddh_handle h, int index, double a, double b, int *nsingular_h, void *stream);
 int ddh_ellband_solve(ddh_handle h, int index, const double *rhs_d, double *x_d, void *stream);
 int ddh_ellband_info(ddh_handle h, int *nw, int *wt, long *factor_bytes);
