@@ -123,6 +123,29 @@ class RealFourier(Basis):
         v[0] = self.length
         return v
 
+    # ---- matrices along this axis when it is the pencil axis of a triply periodic box ------------------
+    def valid_modes(self):
+        """The -sin slot of m = 0 is not a mode (basis.py:1123-1134)."""
+        v = np.ones(self.size, dtype=bool)
+        v[1] = False
+        return v
+
+    def differentiate_matrix(self):
+        """DifferentiateRealFourier (basis.py:1233-1260) on interleaved (cos, -sin) coefficients: per wavenumber the
+        2 x 2 block k [[0, -1], [1, 0]]."""
+        k = self.mode_wavenumbers
+        n = self.size // 2
+        rows = np.concatenate([2 * np.arange(n), 2 * np.arange(n) + 1])
+        cols = np.concatenate([2 * np.arange(n) + 1, 2 * np.arange(n)])
+        vals = np.concatenate([-k, k])
+        keep = vals != 0.0
+        return sparse.csr_matrix((vals[keep], (rows[keep], cols[keep])), shape=(self.size, self.size))
+
+    def convert_matrix(self, out_basis):
+        if out_basis != self:
+            raise ValueError("incompatible Fourier bases")
+        return sparse.identity(self.size, format="csr")
+
 
 def resolve_position(basis, position):
     """'left' / 'right' / 'center' -> coordinate (operators.py Interpolate._preprocess_args role)."""

@@ -47,6 +47,7 @@ class Distributor:
         else:
             self.pcomm = None
         self._jacobi_axes = set()
+        self._pencil_fourier = set()        # a RealFourier axis that takes the Jacobi axis' place (triply periodic boxes)
         self._layout_frozen = False
         self._executor = executor
         self.transformer = Transformer(self)
@@ -80,20 +81,38 @@ class Distributor:
                 if self._layout_frozen:
                     raise ValueError("a Jacobi basis appeared on a new axis after fields were allocated")
                 self._jacobi_axes.add(ax)
+        # more than two separable axes (dim 3, every basis separable): the LAST axis becomes the pencil axis -- first in
+        # storage order, its modes the rows of the system vectors, the grid space sharded along it -- like a Jacobi axis
+        if (self.dim == 3 and not self._jacobi_axes and not self._pencil_fourier
+                and all(b is not None and b.separable for b in domain.by_axis)):
+            if self._layout_frozen:
+                raise ValueError("a third Fourier basis appeared after fields were allocated")
+            if getattr(domain.by_axis[-1], "kind", None) != "rf":
+                raise NotImplementedError("the pencil axis of a triply periodic box must be a RealFourier basis")
+            self._pencil_fourier.add(self.dim - 1)
         if sum(b is not None for b in domain.by_axis) > 1:
             self._layout_frozen = True
-        if len(self._jacobi_axes) > 1:
+        if len(self._jacobi_axes) + len(self._pencil_fourier) > 1:
             raise NotImplementedError("at most one Jacobi (coupled) axis is supported in this round")
 
     @property
+    def coupled_axes(self):
+        """The pencil axis: the Jacobi axis, or the Fourier axis that takes its place in a triply periodic box."""
+        return self._jacobi_axes | self._pencil_fourier
+
+    def is_pencil_axis(self, axis):
+        return axis in self._jacobi_axes or axis in self._pencil_fourier
+
+    @property
     def storage_order(self):
-        jac = sorted(self._jacobi_axes)
-        return tuple(jac + [ax for ax in range(self.dim) if ax not in self._jacobi_axes])
+        cpl = self.coupled_axes
+        return tuple(sorted(cpl) + [ax for ax in range(self.dim) if ax not in cpl])
 
     @property
     def separable_axes(self):
         """User axes of the separable (Fourier) directions, in storage order."""
-        return tuple(ax for ax in self.storage_order if ax not in self._jacobi_axes)
+        cpl = self.coupled_axes
+        return tuple(ax for ax in self.storage_order if ax not in cpl)
 
     # ---- sharding (1-D mesh): coefficient space along the first separable axis, grid space along the
     #      Jacobi axis; everything else is local
@@ -104,7 +123,7 @@ class Distributor:
 
     @property
     def shard_grid_axis(self):
-        jac = sorted(self._jacobi_axes)
+        jac = sorted(self.coupled_axes)
         return jac[0] if (self.size > 1 and jac) else None
 
     def local_block(self, n):
@@ -115,7 +134,7 @@ class Distributor:
         return self.rank * blk, (self.rank + 1) * blk
 
     def coupled_size(self, domain):
-        for ax in self._jacobi_axes:
+        for ax in self.coupled_axes:
             b = domain.by_axis[ax]
             if b is not None:
                 return b.coeff_size

@@ -140,7 +140,7 @@ class Field(HostMirror, Operand):
             raise NotImplementedError("only float64 fields are implemented in this round")
         self.domain = Domain(dist, bases)
         dist._register_domain(self.domain)
-        if getattr(dist, "_pencil_geom", None) is None and dist._jacobi_axes | set(
+        if getattr(dist, "_pencil_geom", None) is None and dist.coupled_axes | set(
                 ax for ax, b in enumerate(self.domain.by_axis) if b is not None) == set(range(dist.dim)) and all(
                 self.domain.by_axis[ax] is not None for ax in dist.separable_axes):
             from .evaluator import set_pencil_geom

@@ -80,6 +80,12 @@ def _sep_index(dist, axis):
     return dist.separable_axes.index(axis)
 
 
+def _cell_axis(dist, b, axis):
+    """Is `axis` (basis b) one of the separable axes of the pencil cells?  (not the Fourier axis that serves as the
+    pencil axis of a triply periodic box: that one acts through matrices along the pencil, like a Jacobi axis)"""
+    return b.separable and axis not in getattr(dist, "_pencil_fourier", ())
+
+
 def convert_linexpr(le, dist, dom_in, dom_out):
     """Convert coefficient data from dom_in to dom_out bases (Convert.operate, operators.py:1628-1640;
     ConvertJacobi basis.py:643-657; ConvertConstant* basis.py:660-676, 1180-1195)."""
@@ -88,9 +94,9 @@ def convert_linexpr(le, dist, dom_in, dom_out):
             continue
         if bo is None:
             raise ValueError("cannot convert away a basis")
-        if bo.separable:
-            if bi is not None:
-                raise ValueError("incompatible Fourier bases")
+        if bo.separable and bi is not None:
+            raise ValueError("incompatible Fourier bases")
+        if _cell_axis(dist, bo, ax):
             le = le.fourier_pin(_sep_index(dist, ax), 1.0 / bo.constant_mode_value)
         else:
             if bi is None:
@@ -150,7 +156,7 @@ class Differentiate(LinearOperator):
         b = self.operand.domain.by_axis[self.axis]
         if b is None:
             return le.scaled(0.0)
-        if b.separable:
+        if _cell_axis(self.dist, b, self.axis):
             return le.fourier_diff(_sep_index(self.dist, self.axis))
         return le.apply_z(b.differentiate_matrix())
 
@@ -170,6 +176,9 @@ class Interpolate(LinearOperator):
             return le
         if b.separable:
             if ctx is not None and not getattr(ctx, "strict", True):
+                if not _cell_axis(self.dist, b, self.axis):
+                    # the Fourier pencil axis of a triply periodic box: a row vector along the pencil, like a Jacobi axis
+                    return le.apply_z(sparse.csr_matrix(b.interpolate_vector(self.position)[None, :]))
                 # run-time evaluation: a reduction of its own (core/reduced.py), a leaf of the expression above it
                 return LinExpr.identity(self, self.ncomp, self.dist.coupled_size(self.domain))
             raise NotImplementedError("interpolation along a Fourier axis couples all modes: unsupported")
@@ -213,7 +222,7 @@ class Integrate(LinearOperator):
             b = self.operand.domain.by_axis[ax]
             if b is None:
                 raise ValueError("cannot integrate along an axis without a basis")
-            if b.separable:
+            if _cell_axis(self.dist, b, ax):
                 # integ cos(kx) dx = L delta_k0 (IntegrateRealFourier basis.py:1304-1325)
                 le = le.fourier_pin(_sep_index(self.dist, ax), 1.0 if self.average else b.length)
             else:
@@ -522,6 +531,20 @@ class CrossProduct(Future):
         self.tensorsig = a.tensorsig
 
     def lin(self, ctx):
+        a, b = self.args
+        lhs = ctx is not None and getattr(ctx, "strict", True)      # (right-hand sides keep evaluating it on the grid)
+        for (c, x, c_first) in ((a, b, True), (b, a, False)):
+            if lhs and _is_const_field(c, ctx):         # a constant vector (f ez x u): linear in the other factor
+                vals = np.asarray(c["g"], dtype=float).reshape(3)
+
+                def fn(co, c_first=c_first, vals=vals):
+                    out = []
+                    for (i, ia, ib, cf) in self.bilinear_terms():
+                        ic, ix = (ia, ib) if c_first else (ib, ia)
+                        if ix == co and vals[ic] != 0.0:
+                            out.append((i, cf * vals[ic]))
+                    return out
+                return x.lin(ctx).comp_map(fn, nco=3)
         return _nonlinear_leaf(self, ctx, "cross product is evaluated on the grid")
 
     def bilinear_terms(self):

@@ -88,6 +88,7 @@ class SolverBase:
         # ---- matrices as term lists (physical row / column numbering)
         self.M_tl = self._assemble("M")
         self.L_tl = self._assemble("L")
+        self._make_invalid_modes_inert()
         self._decouple_boundary_rows()
         self.pack = self.ex.make_pack(nf, self.R, nx, ny, kx, ky, dist._mx_offset)
         self.M_id = self.pack.add_matrix(self.M_tl)
@@ -95,6 +96,91 @@ class SolverBase:
         self._build_recombination()
         self._build_ordering()
         self._build_F_plan()
+        self._build_modal()
+
+    # ---- triply periodic boxes: a Fourier pencil axis ------------------------------------------------------------
+    def _make_invalid_modes_inert(self):
+        """A RealFourier pencil axis has an invalid mode, the msin slot of kz = 0 (core/basis.py RealFourier.valid_modes;
+        the reference drops it, core/subsystems.py:540-556).  Its rows and columns are taken out of M and L; L gets an
+        identity entry that pairs the k-th such row with a such column, so that the slot stays what it is -- zero --
+        through mat-vecs and solves.  A row is paired with the column it meets in a wavenumber-free real entry (the
+        diagonal of a time derivative or a Laplacian) where there is one: that keeps the real grading of the pencils."""
+        self.inert_rows = self.inert_cols = np.zeros(0, dtype=np.int64)
+        pf = sorted(getattr(self.dist, "_pencil_fourier", ()))
+        if not pf:
+            return
+        from ..pencilpack import TermList
+
+        def slots(infos, domain_of):
+            out = []
+            for i in infos:
+                b = domain_of(i).by_axis[pf[0]]
+                if b is not None:
+                    bad = np.flatnonzero(~b.valid_modes())
+                    out += [i["row0"] + c * i["nz"] + int(z) for c in range(i["ncomp"]) for z in bad]
+            return out
+
+        rows = slots(self.eq_info, lambda i: i["eq"]["domain"])
+        cols = slots(self.var_info, lambda i: i["field"].domain)
+        if len(rows) != len(cols):
+            raise ValueError("invalid modes of the equations and of the variables do not balance")
+        met = set()
+        for tl in (self.M_tl, self.L_tl):
+            plain = (tl.ex == 0) & (tl.ey == 0) & (tl.dx == 0) & (tl.dy == 0) & (tl.coef.imag == 0)
+            met |= set(zip(tl.row[plain].tolist(), tl.col[plain].tolist()))
+        pairs, free = {}, list(cols)
+        for r in rows:
+            hit = [c for c in free if (r, c) in met]
+            if hit:
+                pairs[r] = hit[0]
+                free.remove(hit[0])
+        for r in rows:
+            if r not in pairs:
+                pairs[r] = free.pop(0)
+
+        def without(tl, extra=()):
+            keep = ~np.isin(tl.row, rows) & ~np.isin(tl.col, cols)
+            er = np.array([r for r, _ in extra], dtype=np.int32)
+            ec = np.array([c for _, c in extra], dtype=np.int32)
+            z = np.zeros(len(extra), dtype=np.int8)
+            return TermList(tl.nrows, tl.ncols, np.concatenate([tl.row[keep], er]), np.concatenate([tl.col[keep], ec]),
+                            np.concatenate([tl.coef[keep], np.ones(len(extra), dtype=complex)]),
+                            np.concatenate([tl.ex[keep], z]), np.concatenate([tl.ey[keep], z]),
+                            np.concatenate([tl.dx[keep], z]), np.concatenate([tl.dy[keep], z]))
+
+        self.M_tl = without(self.M_tl)
+        self.L_tl = without(self.L_tl, sorted(pairs.items()))
+        self.inert_rows, self.inert_cols = np.array(rows, dtype=np.int64), np.array(cols, dtype=np.int64)
+
+    BAND_KLMAX = 16                         # (KLMAX of csrc/ddh_pencil.hip)
+
+    def _build_modal(self):
+        """The matrix-free modal solve (core/modal.py, csrc/ddh_modal.hip) for a problem with a Fourier pencil axis on an
+        executor that has it; otherwise -- more than 8 component rows, the executors of the tests, DDH_MODAL=0 -- the
+        band LU over the pencil, whose bandwidth is about twice the number of component rows."""
+        self.modal = None
+        self._modal_lus = []
+        if not getattr(self.dist, "_pencil_fourier", None):
+            return
+        reason = "DDH_MODAL=0"
+        if not hasattr(self.ex, "make_modal"):
+            reason = "the executor has no modal solve"
+        elif os.environ.get("DDH_MODAL", "1") != "0":
+            from .modal import plan_from_solver
+            plan, reason = plan_from_solver(self)
+            if plan is not None:
+                self.modal = self.ex.make_modal(plan)
+                return
+        if max(self.kl, 0) > self.BAND_KLMAX:
+            raise NotImplementedError("triply periodic problem without the modal solve (%s): the band LU over the pencil "
+                                      "needs %d sub-diagonals, its limit is %d" % (reason, self.kl, self.BAND_KLMAX))
+        logger.info("triply periodic problem on the band LU over the pencil (%s)" % reason)
+
+    def factor_bytes(self):
+        """Device memory held by the factorizations of the implicit systems (0 for the matrix-free modal solve)."""
+        if self.modal is not None:
+            return 0
+        return sum(int(self.pack.lu_bytes(lu)) for lu in getattr(self, "_lu_params", {}))
 
     # ---- assembly ----------------------------------------------------------------------------------------
     def _flags(self, domain):
@@ -855,6 +941,8 @@ class SolverBase:
             return False
         if self.nf != 2 or self.nx % 8 or self.ny % 8 or self.dist.size > 1:
             return False
+        if getattr(self.dist, "_pencil_fourier", None):
+            return False                        # (the backward z transforms of a Fourier pencil axis read natural rows)
         if self.nx * self.ny < int(os.environ.get("DDH_X_TILED_MIN", 4 * 16384)):
             return False
         sep = self.dist.separable_axes
@@ -962,7 +1050,10 @@ class SolverBase:
 
     def solve(self, lu, rhs, out):
         """out = (a M + b L)^-1 rhs  through the recombined band factorization: X = P Y."""
-        if self.P_id is None:
+        if getattr(self, "modal", None) is not None:
+            a, b = self._modal_lus[lu]
+            self.modal.solve(a, b, [rhs], [1.0], out)
+        elif self.P_id is None:
             self.pack.solve(lu, rhs, out)
         elif hasattr(self.pack, "solve_recombined"):
             Y = self.ex.empty((self.R, self.nx, self.ny))
@@ -1060,6 +1151,17 @@ class SolverBase:
         """out = (a M + b L)^-1 (sum_t alphas[t] xs[t]).  The combination is formed inside the forward sweep of the band
         solve; with a parity probe attached (or more terms than the kernel takes) it is materialised first."""
         probe = getattr(self, "solve_probe", None)
+        if getattr(self, "modal", None) is not None and probe is None and len(xs) <= self.modal.MAX_RHS_TERMS and not tiled:
+            a, b = self._modal_lus[lu]
+            self.modal.solve(a, b, xs, alphas, out)         # (the combination is formed while the cells are loaded)
+            return
+        if getattr(self, "modal", None) is not None:
+            if tiled:
+                raise RuntimeError("tile-major right-hand sides need the fused recombined solve")
+            rhs = self.ex.empty((self.R, self.nx, self.ny))
+            self.ex.lincomb(rhs, xs, alphas)
+            self._last_rhs = rhs
+            return self.solve(lu, rhs, out)
         if tiled and (self.P_id is None or not hasattr(self.pack, "solve_recombined") or len(xs) > self.pack.MAX_RHS_TERMS):
             raise RuntimeError("tile-major right-hand sides need the fused recombined solve")
         if len(xs) > self.pack.MAX_RHS_TERMS or not hasattr(self.pack, "solve_lincomb"):
@@ -1159,6 +1261,17 @@ class SolverBase:
         return np.concatenate(parts)
 
     def factor(self, a, b, reuse=-1):
+        if getattr(self, "modal", None) is not None:
+            # nothing to factor: the id names the pair (a, b) the modal solve assembles its systems with
+            if reuse >= 0:
+                lu = reuse
+                self._modal_lus[lu] = (float(a), float(b))
+            else:
+                lu = len(self._modal_lus)
+                self._modal_lus.append((float(a), float(b)))
+            self.__dict__.setdefault("_lu_params", {})[lu] = (float(a), float(b))
+            return lu
+        self.factor_calls = getattr(self, "factor_calls", 0) + 1
         lu = self.pack.factor(self.MP_id, self.LP_id, a, b, self.row_perm, self.col_perm, self.n_interior,
                               self.kl, self.ku, self.row_axes, self.col_axes, reuse=reuse,
                               real=self.real_grading)

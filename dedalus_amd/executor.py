@@ -572,6 +572,10 @@ class HipExecutor:
         pk.executor = self
         return pk
 
+    def make_modal(self, plan):
+        """Matrix-free modal solve of a triply periodic box (ddh_modal_create; `plan`: core/modal.py::ModalPlan)."""
+        return ModalSolve(self, plan)
+
 
 class _AsyncDownload:
     def __init__(self, host, done, shape, pool):
@@ -726,6 +730,55 @@ class EllTerms:
         if self.dense_part is not None:
             libhip.note_cost("ddh_ell_terms_apply_acc", 2.0 * self.dense_part._madds, self.dense_part._mat_bytes + (x.numel() + y.numel()) * 8)
             libhip.call("ddh_ell_terms_apply_acc", self.dense_part.handle, ptr(x), ptr(y), 1, self.ex.dev.stream)
+
+    def __del__(self):
+        try:
+            libhip.call("ddh_destroy", self.handle)
+        except Exception:
+            pass
+
+
+class ModalSolve:
+    """ddh_modal_create / ddh_pencil_solve_modal: the rc x rc complex systems of every Fourier mode of a triply periodic
+    box, assembled from the symbol term list and eliminated in registers on every solve (nothing stored)."""
+
+    MAX_RHS_TERMS = 8
+
+    def __init__(self, ex, plan):
+        self.ex, self.plan = ex, plan
+        u8 = lambda a: np.ascontiguousarray(a, dtype=np.uint8)
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        kx, ky, kz = f64(plan.kx), f64(plan.ky), f64(plan.kz)
+        rr, xr, ax = i32(plan.rhs_row), i32(plan.x_row), u8(plan.axes)
+        ti, tj = i32(plan.ti), i32(plan.tj)
+        cre, cim = f64(np.real(plan.coef)), f64(np.imag(plan.coef))
+        exs, eys, ezs, fl = u8(plan.ex), u8(plan.ey), u8(plan.ez), u8(plan.flags)
+        self.handle = C.c_uint64(0)
+        libhip.call("ddh_modal_create", C.byref(self.handle), int(plan.rc), int(plan.nx), int(plan.ny), int(plan.nz),
+                    libhip.as_dp(kx), libhip.as_dp(ky), libhip.as_dp(kz), int(plan.mx_offset), int(plan.nrows_rhs),
+                    int(plan.nrows_x), libhip.as_ip(rr), libhip.as_ip(xr), libhip.as_ubp(ax), int(ti.size), libhip.as_ip(ti),
+                    libhip.as_ip(tj), libhip.as_dp(cre), libhip.as_dp(cim), libhip.as_ubp(exs), libhip.as_ubp(eys),
+                    libhip.as_ubp(ezs), libhip.as_ubp(fl))
+
+    def solve(self, a, b, xs, alphas, x, rhs_tiled=False, x_tiled=False):
+        """x = (a M + b L)^-1 sum_t alphas[t] xs[t]"""
+        if self.ex.timer is not None:
+            nb = (sum(v.numel() for v in xs) + x.numel()) * 8
+            return self.ex.timer.run("pencil_solve_modal", nb, self._solve, a, b, xs, alphas, x, rhs_tiled, x_tiled)
+        return self._solve(a, b, xs, alphas, x, rhs_tiled, x_tiled)
+
+    def _solve(self, a, b, xs, alphas, x, rhs_tiled, x_tiled):
+        p = self.plan
+        for v in xs:
+            if v.numel() < p.nrows_rhs * p.nx * p.ny:
+                raise ValueError("modal solve: right-hand side smaller than %d rows" % p.nrows_rhs)
+        if x.numel() < p.nrows_x * p.nx * p.ny:
+            raise ValueError("modal solve: solution vector smaller than %d rows" % p.nrows_x)
+        arr = (C.c_void_p * len(xs))(*[C.c_void_p(v.data_ptr()) for v in xs])
+        al = np.ascontiguousarray(alphas, dtype=np.float64)
+        libhip.call("ddh_pencil_solve_modal", self.handle, float(a), float(b), len(xs), arr, libhip.as_dp(al),
+                    int(bool(rhs_tiled)), ptr(x), int(bool(x_tiled)), self.ex.dev.stream)
 
     def __del__(self):
         try:

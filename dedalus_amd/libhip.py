@@ -143,6 +143,10 @@ SIGNATURES = {
     "ddh_pencil_lu_bytes": [_h, _i, C.POINTER(C.c_size_t)],
     "ddh_pencil_lu_info": [_h, _i, _ip],
     "ddh_pencil_lu_row_widths": [_h, _i, _ip],
+    "ddh_modal_create": [_hp, _i, _l, _l, _l, _dp, _dp, _dp, _l, _i, _i, _ip, _ip, C.POINTER(C.c_ubyte), _i, _ip, _ip,
+                         _dp, _dp, C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte)],
+    "ddh_pencil_solve_modal": [_h, _d, _d, _i, C.POINTER(_vp), _dp, _i, _vp, _i, _vp],
+    "ddh_modal_launches": [C.POINTER(_l)],
     "ddh_comm_probe": [],
     "ddh_comm_unique_id": [C.POINTER(C.c_ubyte)],
     "ddh_comm_create": [_hp, _i, _i, C.POINTER(C.c_ubyte)],

@@ -583,6 +583,31 @@ int ddh_pencil_lu_info(ddh_handle pack, int lu_id, int *info_h);
  * how much of the partial-pivoting fill space (kl extra super-diagonals, LAPACK gbtrf storage) is really used.  */
 int ddh_pencil_lu_row_widths(ddh_handle pack, int lu_id, int *wrow_h);
 
+/* ---- triply periodic boxes: matrix-free modal solve (csrc/ddh_modal.hip) ------------------------------------------
+ * Three real-Fourier axes: the z modes are the rows of the system vectors, [row][nx][ny] with row = first row of a tensor
+ * component + 2 mz + (0 cos, 1 msin), one row for a component without a z basis.  Every mode (mx, my, mz) is a cell of 8
+ * reals per component = four independent rc x rc complex systems (a M + b L)(+-kx, ky, +-kz) X = W (P, Q of the cos_z and
+ * msin_z rows: W = P_c +- i P_s, Q_c +- i Q_s).  The plan holds the geometry, the rows of the rc component rows in the
+ * right-hand-side and solution vectors, their axes bits (1 x, 2 y, 4 z basis: a component is an identity row / column of
+ * every cell in which it has no mode) and the symbol term list
+ *     A[ti, tj] += (flags & 8 ? b : a) * coef * kx^ex * ky^ey * kz^ez * [mx == 0]^(flags & 1) [my == 0]^(flags & 2) [mz == 0]^(flags & 4)
+ * with exponents 0 .. 4 (powers of i folded into coef).  kx_h / ky_h / kz_h: nx / 2, ny / 2, nz / 2 wavenumbers.
+ * ddh_pencil_solve_modal: x = (a M + b L)^-1 sum_t alphas_h[t] rhs[t] (nrhs <= 8 device vectors), assembled and
+ * eliminated with partial pivoting in registers on every call: nothing is stored between solves.  rhs_tiled / x_tiled:
+ * the rows of those vectors are tile-major [kx / 8][ky / 8][kx % 8][ky % 8] (nx, ny multiples of 8).  Real slots that
+ * hold no mode (msin of wavenumber 0, components without a mode in the cell) are never read and are written as +0.
+ * x may be one of the right-hand sides when both use the same layout.  The systems are those the reference factors per
+ * subproblem (core/subsystems.py:497-596, libraries/matsolvers.py:126-149).                                          */
+int ddh_modal_create(ddh_handle *out, int rc, long nx, long ny, long nz, const double *kx_h, const double *ky_h,
+                     const double *kz_h, long mx_offset, int nrows_rhs, int nrows_x, const int *rhs_row_h,
+                     const int *x_row_h, const unsigned char *axes_h, int nterms, const int *ti_h, const int *tj_h,
+                     const double *coef_re_h, const double *coef_im_h, const unsigned char *ex_h,
+                     const unsigned char *ey_h, const unsigned char *ez_h, const unsigned char *flags_h);
+int ddh_pencil_solve_modal(ddh_handle plan, double a, double b, int nrhs, const double *const *rhs, const double *alphas_h,
+                           int rhs_tiled, double *x, int x_tiled, void *stream);
+/* Diagnostic: launches of the modal solve by this process (as ddh_fft_wave_launches). */
+int ddh_modal_launches(long *count);
+
 /* ---- distributed transposes (boundary B3) ------------------------------------ */
 /* Communicator: one process per GPU, RCCL over xGMI, owned by the library (replaces the mpi4py communicator the
  * reference plans its transposes on, core/distributor.py:696-768).  Rank 0 obtains an id and hands it to the other
