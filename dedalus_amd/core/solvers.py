@@ -1147,9 +1147,50 @@ class SolverBase:
             self._skiprows = self._device_mask(mask)
         return self._skiprows
 
-    def solve_lincomb(self, lu, xs, alphas, out, zero_rows=None, skip_rows=None, tiled=False):
+    MX_WINDOW = 18          # y_j .. y_(j+17): the register window of the backward sweep that emits M.X (csrc/ddh_pencil.hip MXW)
+
+    def mx_band_tables(self, rows_per_block=None, width=None):
+        """(row [n] int16, band [n][width]) for the backward sweep that writes M.X (`mx_band_tables` below) from the
+        graded term list of M P in this solver's ordering, or None when the sweep cannot form the product.
+        rows_per_block: the independent diagonal blocks the sweeps run per thread (None: one block)."""
+        if self.P_tl is None or self.real_grading is None or self.n_interior <= 0:
+            return None
+        tl = self.MP_tl.consolidated()
+        if np.any(tl.ex) or np.any(tl.ey) or np.any(tl.dx) or np.any(tl.dy):
+            return None
+        n = int(self.n_interior)
+        return mx_band_tables(tl.row, tl.col, tl.coef, self.row_perm, self.col_perm, n, int(rows_per_block or n),
+                              self.real_grading["row_code"], self.real_grading["col_code"],
+                              int(width or self.MX_WINDOW))
+
+    def prepare_mx_emission(self, lu):
+        """Whether the sweeps of factorization `lu` can write M.X (PencilPack.emits_mx) and the analysis of M P allows it;
+        hands the tables of `mx_band_tables` to the factorization when both hold."""
+        if not hasattr(self.pack, "emits_mx") or self.P_id is None or getattr(self, "modal", None) is not None:
+            return False
+        if not self.pack.emits_mx(lu, self.P_id):
+            return False
+        info = self.pack.lu_info(lu)
+        tables = self.mx_band_tables(info["rows_per_block"] if info["nsplit"] > 1 else None)
+        if tables is None:
+            return False
+        self.pack.set_mx_band(lu, self.M_id, tables[0], tables[1])
+        return True
+
+    def sweep_emits_mx(self, lus):
+        """Whether the timestepper lets the tiled solves of EVERY factorization in `lus` write M.X of their solution from the
+        backward sweep (`prepare_mx_emission`): one rank, a tile-major state; asked again after every refactorization and
+        change of the sweep variant, like `rhs_tiling`."""
+        if self.dist.size > 1 or not getattr(self, "x_tiled", 0):
+            return False
+        return all(self.prepare_mx_emission(lu) for lu in lus)
+
+    def solve_lincomb(self, lu, xs, alphas, out, zero_rows=None, skip_rows=None, tiled=False, mx_out=None):
         """out = (a M + b L)^-1 (sum_t alphas[t] xs[t]).  The combination is formed inside the forward sweep of the band
-        solve; with a parity probe attached (or more terms than the kernel takes) it is materialised first."""
+        solve; with a parity probe attached (or more terms than the kernel takes) it is materialised first.
+        mx_out (tiled solves where `sweep_emits_mx` holds): the backward sweep also writes M.out there."""
+        if mx_out is not None and not (tiled and self.P_id is not None and len(xs) <= self.pack.MAX_RHS_TERMS):
+            raise RuntimeError("M.X from the sweep needs the tiled fused recombined solve")
         probe = getattr(self, "solve_probe", None)
         if getattr(self, "modal", None) is not None and probe is None and len(xs) <= self.modal.MAX_RHS_TERMS and not tiled:
             a, b = self._modal_lus[lu]
@@ -1185,9 +1226,14 @@ class SolverBase:
         elif hasattr(self.pack, "solve_recombined"):
             Y = self.ex.empty((self.R, self.nx, self.ny))
             if tiled:
-                self.pack.solve_recombined(lu, xs, alphas, self.P_id, Y, out, zero_rows=zero_rows, skip_rows=skip_rows,
-                                           tiled=True)
-                path = "ddh_pencil_solve_recombined_tiled"
+                if mx_out is not None:
+                    self.pack.solve_recombined(lu, xs, alphas, self.P_id, Y, out, zero_rows=zero_rows, skip_rows=skip_rows,
+                                               tiled=True, mx=(self.M_id, mx_out))
+                    path = "ddh_pencil_solve_recombined_tiled_mx"
+                else:
+                    self.pack.solve_recombined(lu, xs, alphas, self.P_id, Y, out, zero_rows=zero_rows, skip_rows=skip_rows,
+                                               tiled=True)
+                    path = "ddh_pencil_solve_recombined_tiled"
             elif zero_rows is not None or skip_rows is not None:
                 self.pack.solve_recombined(lu, xs, alphas, self.P_id, Y, out, zero_rows=zero_rows, skip_rows=skip_rows)
                 path = "ddh_pencil_solve_recombined_sparse"
@@ -1449,6 +1495,57 @@ class SolverBase:
             logger.warning("explicit block inverses: ||B^T X - I|| = %.1e > %.0e, the sweeps stay" % (worst, tol))
             return False
         return True
+
+
+def mx_band_tables(row, col, coef, row_perm, col_perm, n, nh, row_code, col_code, width):
+    """Tables of the M.X emission of the backward sweep (csrc/ddh_pencil.hip, MxEmit).
+
+    row, col, coef: the consolidated, wavenumber-independent term list of M P (physical indices); row_perm / col_perm:
+    logical -> physical; n band rows in blocks of nh; row_code / col_code: grading codes per PHYSICAL row / column.
+    When step j of the backward sweep ends, its register window holds y_j .. y_(j + width - 1) of x = P y.  Every
+    logical row i of M P with entries gets a step t of its own (step_row[t] = i, -1: none) in the block of its columns
+    with all its columns in [t, t + width): band[t, d] = (M P)[i, t + d].  Rows are placed greedily, largest first column
+    first, at the largest free step <= their first column.  Returns None when that is impossible: a complex entry, an
+    entry in a border row / column, a row whose columns span two blocks or two grading classes (the graded coefficient
+    would not be the plain one), a row wider than the window, or no free step."""
+    R = len(row_perm)
+    rinv = np.empty(R, dtype=np.int64)
+    cinv = np.empty(R, dtype=np.int64)
+    rinv[np.asarray(row_perm)] = np.arange(R)
+    cinv[np.asarray(col_perm)] = np.arange(R)
+    coef = np.asarray(coef)
+    keep = coef != 0
+    row, col, coef = np.asarray(row)[keep], np.asarray(col)[keep], coef[keep]
+    if coef.size and np.any(np.abs(coef.imag) > 0):
+        return None
+    i, j = rinv[row], cinv[col]
+    if np.any(i >= n) or np.any(j >= n):
+        return None
+    if np.any(np.asarray(row_code)[row] != np.asarray(col_code)[col]):
+        return None
+    step_row = -np.ones(n, dtype=np.int16)
+    band = np.zeros((n, width))
+    if n > 32767:
+        return None
+    rows = []
+    for r in np.unique(i):
+        cols = j[i == r]
+        if np.any(cols // nh != cols[0] // nh):
+            return None
+        if cols.max() - cols.min() >= width:
+            return None
+        rows.append((int(cols.min()), int(cols.max()), int(r)))
+    for cmin, cmax, r in sorted(rows, key=lambda v: (-v[0], -v[1])):
+        lo = max(cmax - (width - 1), 0, (cmin // nh) * nh)
+        t = cmin
+        while t >= lo and step_row[t] >= 0:
+            t -= 1
+        if t < lo:
+            return None
+        step_row[t] = r
+        m = i == r
+        np.add.at(band[t], j[m] - t, coef[m].real)
+    return step_row, band
 
 
 def _two_colour(n, row, col, label):

@@ -82,10 +82,12 @@ class _SolveMixin:
             self._RHS = s.ex.zeros((s.R, s.nx, s.ny))
         return self._RHS
 
-    def _solve_combination(self, xs, al, lu, zero_rows=None, skip_rows=None, tiled=False):
+    def _solve_combination(self, xs, al, lu, zero_rows=None, skip_rows=None, tiled=False, mx_out=None):
         s = self.solver
         if hasattr(s, "solve_lincomb"):
-            if tiled:
+            if mx_out is not None:
+                s.solve_lincomb(lu, xs, al, s.X, zero_rows=zero_rows, skip_rows=skip_rows, tiled=True, mx_out=mx_out)
+            elif tiled:
                 s.solve_lincomb(lu, xs, al, s.X, zero_rows=zero_rows, skip_rows=skip_rows, tiled=True)
             elif zero_rows is not None or skip_rows is not None:
                 s.solve_lincomb(lu, xs, al, s.X, zero_rows=zero_rows, skip_rows=skip_rows)
@@ -348,6 +350,9 @@ class RungeKuttaIMEX(_SolveMixin):
                             for j in range(1, self.stages + 1)]
         self._k = None
         self._lus = {}          # H_ii -> lu id
+        # M.X of the state from the backward sweep of the solve that wrote it (SolverBase.sweep_emits_mx): the iteration
+        # whose start state the last stage's sweep left in MX0, or None
+        self._mx0_iteration = None
 
     def step(self, dt, wall_time=None):
         s = self.solver
@@ -364,7 +369,10 @@ class RungeKuttaIMEX(_SolveMixin):
                 if h not in self._lus:
                     self._lus[h] = s.factor(1.0, k * h, reuse=(reuse.pop() if reuse else -1))
             self._k = k
+            self._mx0_iteration = None
         t0 = s.sim_time
+        # (asked BEFORE the synchronisation, which uploads a host edit and leaves the state looking untouched)
+        state_kept = bool(getattr(s, "_state_is_clean", lambda: False)())
         s.sync_state_to_device()
         own = dict(owned=True) if getattr(pack, "supports_zero_rows", False) else {}
         # the M.X and F buffers of this timestepper in the tile-major layout the sweeps read contiguously
@@ -381,23 +389,42 @@ class RungeKuttaIMEX(_SolveMixin):
                     ex.fill_zero(buf)
                 s._F_zeroed = set(b.data_ptr() if hasattr(b, "data_ptr") else id(b) for b in self.F)
             self._tiled, self._tiled_stamp = tiled_now, stamp
+            # the sweeps that write M.X themselves: the products of the solved stages are not launched at all
+            self._emit = bool(tiled_now) and hasattr(s, "sweep_emits_mx") and s.sweep_emits_mx(self._lus.values())
+            self._mx0_iteration = None
         tiled = self._tiled
+        emit = self._emit
         if tiled:
             own = dict(owned=True, tiled=True)
+        # MX0 left by the last sweep of the previous step is M.X of this step's start state unless something else wrote
+        # the state since: a user edit, load_state, a transform round trip (IVPLifecycle._state_is_clean: `state_kept`, asked
+        # above before the state was synchronised; the Hermitian round trip is excluded below, where the sweep would emit).  A captured step
+        # (step graph) is replayed whatever happened in between: it always forms MX0 from the state.
+        iteration = getattr(s, "iteration", None)
+        capturing = bool(getattr(s, "_graph_wanted", lambda: False)())
+        mx0_kept = (emit and not capturing and iteration is not None and self._mx0_iteration == iteration
+                    and state_kept)
+        self._mx0_iteration = None
+        cadence = getattr(s, "enforce_real_cadence", 0)
+        mx0_next = (emit and not capturing and iteration is not None and hasattr(s, "_state_is_clean")
+                    and not (cadence and iteration % cadence < self.steps))
         # The mat-vecs of a stage read the state only: a solver whose right-hand-side evaluation has a wait in it (several
         # ranks: the last window's forward exchange, SolverBase.evaluate_F) takes them as work to issue at that point.
         later = []
         defer_mv = bool(getattr(s, "overlaps_rhs_work", lambda: False)())
-        (later.append if defer_mv else (lambda f: f()))(lambda: pack.matvec(s.M_id, s.X, self.MX0, **own))
+        if not mx0_kept:
+            (later.append if defer_mv else (lambda f: f()))(lambda: pack.matvec(s.M_id, s.X, self.MX0, **own))
         combs = {}
         for i in range(1, self.stages + 1):
             j = i - 1                                   # s.X holds X_j
             if self._need_lx[j]:
+                mv = None
                 if self._direct or j == 0:
                     mv = (lambda j=j: pack.matvec(s.L_id, s.X, self.LX[j]))
-                else:
+                elif not emit:                          # (else: written by the sweep of stage j's solve)
                     mv = (lambda j=j: pack.matvec(s.M_id, s.X, self.MX[j], **own))
-                (later.append if defer_mv else (lambda f: f()))(mv)
+                if mv is not None:
+                    (later.append if defer_mv else (lambda f: f()))(mv)
             if later:
                 s._overlap_work = list(later)
                 del later[:]
@@ -432,9 +459,19 @@ class RungeKuttaIMEX(_SolveMixin):
             skip = None
             if i < self.stages and not self._direct and hasattr(s, "intermediate_skip_rows"):
                 skip = s.intermediate_skip_rows()
-            self._solve_combination(xs, al, self._lus[float(H[i, i])], zero_rows=zrows, skip_rows=skip, tiled=bool(tiled))
+            # M.X of the stage's solution from its own backward sweep: MX[i] where a later stage reads L.X_i, MX0 of the
+            # next step after the last stage
+            mx_out = None
+            if emit and i < self.stages and self.MX[i] is not None:
+                mx_out = self.MX[i]
+            elif i == self.stages and mx0_next:
+                mx_out = self.MX0
+            self._solve_combination(xs, al, self._lus[float(H[i, i])], zero_rows=zrows, skip_rows=skip, tiled=bool(tiled),
+                                    mx_out=mx_out)
             s.mark_state_current()
             s.sim_time = t0 + k * c[i]
+        if mx0_next:
+            self._mx0_iteration = iteration + 1
 
 
 @add_scheme

@@ -140,6 +140,18 @@ struct LuDev {
 
 constexpr int PBW = 12;
 
+// M.X emitted by the backward sweep (ddh_pencil_solve_recombined_tiled_mx).  With the recombination fused the register
+// window of solve_backward_kernel holds y_j .. y_(j + WT) of x = P y when step j ends; row i of the band of M P (graded,
+// logical ordering -- real, wavenumber-independent) whose columns lie in that window is formed there:
+//     band[j * MXW + d] = (M P)[row[j], j + d], d = 0 .. MXW - 1;   row[j] = the logical equation row emitted at step j, -1: none
+// out: tile-major equation-space vector (tile_offset); rows without M entries are never written.
+constexpr int MXW = 18;          // WT + 1 of the WT = 17 instantiation, the only one that emits
+struct MxEmit {
+    double *out;
+    const double *band;
+    const short *row;
+};
+
 struct LuFactor {
     LuDev dev;
     size_t bytes = 0;
@@ -160,6 +172,8 @@ struct LuFactor {
     void *d_pband = nullptr;                // [n][PBW] band of the recombination, see LuDev::pband
     void *d_vcell = nullptr, *d_vslot = nullptr, *d_rowperm2 = nullptr, *d_colperm2 = nullptr;   // partner pencils
     void *d_wrow = nullptr;                 // [n] int, see LuDev::wrow
+    void *d_mxband = nullptr, *d_mxrow = nullptr;   // MxEmit::band / row
+    int mx_mat = -1, mx_ok = 0;                     // ddh_pencil_set_mx_band: the mass matrix of the tables; 1: tables on file
     std::vector<long> slot_cells_h;         // [2 * GL]: the cell of a slot and its partner (-1 = none)
     void *d_slot_cell = nullptr;
     int pband_mat = -1;                     // matrix id it was built from
@@ -209,6 +223,8 @@ static void free_lu(LuFactor *lu) {
     (void)hipFree(lu->d_rowperm2);
     (void)hipFree(lu->d_colperm2);
     (void)hipFree(lu->d_wrow);
+    (void)hipFree(lu->d_mxband);
+    (void)hipFree(lu->d_mxrow);
     delete lu;
 }
 
@@ -2032,10 +2048,11 @@ solve_forward_deep_kernel(PencilDev P, LuDev L, const RhsSrc rhs, double *__rest
     }
 }
 
-template <int NF, int WT, bool REAL, bool PREF, bool PFUSE = false, int MINW = 1>
+template <int NF, int WT, bool REAL, bool PREF, bool PFUSE = false, int MINW = 1, bool EMIT_MX = false>
 __global__ void __launch_bounds__(256, MINW)
 solve_backward_kernel(PencilDev P, LuDev L, double *__restrict__ xout, const double *__restrict__ pband,
-                      const unsigned char *__restrict__ skip) {
+                      const unsigned char *__restrict__ skip, MxEmit mx) {
+    static_assert(!EMIT_MX || (PFUSE && REAL && NF == 2 && WT + 1 == MXW), "M.X is emitted from the window of y = P^-1 x");
     typedef typename El<REAL>::T E;
     extern __shared__ int s_lds[];
     const int n = L.n, nb = L.nb, kl = L.kl, W = L.W;
@@ -2044,7 +2061,9 @@ solve_backward_kernel(PencilDev P, LuDev L, double *__restrict__ xout, const dou
     unsigned char *s_code = (unsigned char *)(s_perm2 + n);
     unsigned char *s_skip = s_code + n;                 // unknowns the caller does not need: not stored
     unsigned char *s_nq = s_skip + n;                   // entry pairs of U row j that can hold data (LuDev::wrow)
+    short *s_mxrow = (short *)(s_nq + n + (n & 1));     // EMIT_MX: the equation row formed at step j (MxEmit::row)
     for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        if (EMIT_MX) s_mxrow[i] = mx.row[i];
         s_perm[i] = L.colperm[i];
         if (L.pair) s_perm2[i] = L.colperm2[i];
         s_code[i] = REAL ? L.col_code[i] : 0;
@@ -2144,6 +2163,45 @@ solve_backward_kernel(PencilDev P, LuDev L, double *__restrict__ xout, const dou
         if (conjq) v.y = -v.y;
         store_sys<NF>(xout, plane, my_perm[j], P, c, s, v);
     };
+    // EMIT_MX: (M P y)[i] for the equation row i = s_mxrow[j] from y_j and the window y_(j + 1 + d) = wv(d) -- the inverse of
+    // the forward sweep's row load (grading code, partner conjugation, system -> real parts), stored tile-major.  The
+    // coefficients and the row are wave-uniform (scalar loads); the lane's address is one 32-bit offset into the buffer
+    // resource of the whole vector (nrows * nx * ny * 8 < 4 GiB, checked by sweep_plan).
+    const __amdgpu_buffer_rsrc_t mx_rs = wave_rsrc(mx.out);      // (unused, and removed, without EMIT_MX)
+    const unsigned mx_lane = EMIT_MX ? (unsigned)(tile_offset(2 * c.mx + s, 2 * c.my, P.ny) * (long)sizeof(double)) : 0u;
+    auto emit_mx = [&](int j, double2 yj, auto wv) {
+        if constexpr (EMIT_MX) {
+            const int mi = __builtin_amdgcn_readfirstlane((int)s_mxrow[j]);
+            if (mi < 0) return;                          // wave-uniform
+            // (the 18 coefficients take 36 scalar registers: requested only now, when those of the factor row's recombination
+            //  band are dead -- hoisted above the row they spill scalar registers into vector lanes, and those to scratch)
+            __builtin_amdgcn_sched_barrier(0);
+            const double *cf = mx.band + (long)j * MXW;
+            double2 a = make_double2(cf[0] * yj.x, cf[0] * yj.y);
+#pragma unroll
+            for (int d = 0; d < WT; ++d) {
+                const double2 w = wv(d);
+                a.x += cf[d + 1] * w.x;
+                a.y += cf[d + 1] * w.y;
+            }
+            const unsigned char code = L.row_code[mi];
+            if (code & 1) a = make_double2(-a.y, a.x);
+            if ((code & 2) && s == 1) a = make_double2(-a.x, -a.y);
+            if (conjq) a.y = -a.y;
+            const int prow = (L.pair && id.partner) ? L.rowperm2[mi] : L.rowperm[mi];
+            double2 other;
+            other.x = __shfl_xor(a.x, 1);
+            other.y = __shfl_xor(a.y, 1);
+            double2 out = (s == 0) ? make_double2(0.5 * (a.x + other.x), 0.5 * (a.y + other.y))
+                                   : make_double2(0.5 * (other.y - a.y), 0.5 * (a.x - other.x));
+            if (c.my == 0) out.y = 0.0;                  // (as store_sys: the msin parts of a k = 0 mode)
+            if (c.gmx == 0 && s == 1) out = make_double2(0.0, 0.0);
+            ddh_u4v q;
+            q.x = (unsigned)__double2loint(out.x); q.y = (unsigned)__double2hiint(out.x);
+            q.z = (unsigned)__double2loint(out.y); q.w = (unsigned)__double2hiint(out.y);
+            __builtin_amdgcn_raw_buffer_store_b128(q, mx_rs, mx_lane + (unsigned)prow * (unsigned)(plane * (long)sizeof(double)), 0, 0);
+        }
+    };
     // rows are processed in pairs; the register window is shifted once per pair (by two).  With PFUSE the emitted value
     // is the recombined unknown x_j = y_j + sum_d P[j, j + d] y_(j + d) (the window already holds y_(j+1..)): the
     // band coefficients are the same for every system -> scalar loads.
@@ -2160,6 +2218,7 @@ solve_backward_kernel(PencilDev P, LuDev L, double *__restrict__ xout, const dou
                 if (d < WT) { v.x += pr[d] * win[d].x; v.y += pr[d] * win[d].y; }
         }
         emit(j, v);
+        emit_mx(j, xj, [&](int d) { return win[d]; });
         return xj;
     };
     auto row_odd = [&](int j, const E *u, double2 y, double2 xprev, const double *pr) {
@@ -2178,6 +2237,7 @@ solve_backward_kernel(PencilDev P, LuDev L, double *__restrict__ xout, const dou
                 if (d - 1 < WT) { v.x += pr[d] * win[d - 1].x; v.y += pr[d] * win[d - 1].y; }
         }
         emit(j, v);
+        emit_mx(j, xj, [&](int d) { return d == 0 ? xprev : win[d > 0 ? d - 1 : 0]; });
 #pragma unroll
         for (int d = WT - 1; d > 1; --d) win[d] = win[d - 2];
         win[1] = xprev;
@@ -2802,9 +2862,43 @@ blockinv_solve_kernel(PencilDev P, LuDev L, const RhsSrc rhs, const double *__re
         for (int r = tid; r < L.nb; r += NT) store_sys<1>(yout, plane, L.colperm[L.n + r], P, c, 0, make_double2(0.0, 0.0));
 }
 
-// dense fallback for the flagged pencils (after either sweep variant)
+// M.X of the flagged pencils after their dense solve (a sweep that emits M.X forms it from the sweep's own, meaningless,
+// solution of those pencils): thread -> (flagged cell, row of M), the terms of the row in matvec_kernel's order and
+// arithmetic, x in the state layout, y tile-major; rows without terms are not written.
+__global__ void __launch_bounds__(256)
+flagged_matvec_tiled_kernel(PencilDev P, MatDev A, const long *__restrict__ cells, int ncellsf, const double *__restrict__ x,
+                            double *__restrict__ y) {
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (long)A.nrows_out * ncellsf) return;
+    const int r = (int)(t % A.nrows_out);
+    const int t0 = A.rowptr[r], t1 = A.rowptr[r + 1];
+    if (t1 == t0) return;
+    const CellCtx c = cell_ctx(P, cells[t / A.nrows_out]);
+    const long xoff0 = state_cell(P, 2 * c.mx, 2 * c.my), xoff1 = state_cell(P, 2 * c.mx + 1, 2 * c.my);
+    double2 accP = make_double2(0.0, 0.0), accQ = accP;
+    for (int k = t0; k < t1; ++k) {
+        const unsigned e = A.expo[k];
+        const double f = term_factor(e, c);
+        const double2 cf = A.coef[k];
+        const double2 v = make_double2(cf.x * f, cf.y * f);
+        const double *xr = x + (long)A.col[k] * state_row_stride(P);
+        const double2 a = *reinterpret_cast<const double2 *>(xr + xoff0);
+        const double2 b = *reinterpret_cast<const double2 *>(xr + xoff1);
+        cfma(accP, v, make_double2(a.x - b.y, a.y + b.x));
+        const double sg = (e & 1u) ? -1.0 : 1.0;
+        cfma(accQ, make_double2(v.x * sg, v.y * sg), make_double2(a.x + b.y, a.y - b.x));
+    }
+    double *yr = y + (long)r * P.nx * P.ny;
+    *reinterpret_cast<double2 *>(yr + tile_offset(2 * c.mx, 2 * c.my, P.ny)) =
+        make_double2(0.5 * (accP.x + accQ.x), 0.5 * (accP.y + accQ.y));
+    *reinterpret_cast<double2 *>(yr + tile_offset(2 * c.mx + 1, 2 * c.my, P.ny)) =
+        make_double2(0.5 * (accP.y - accQ.y), 0.5 * (accQ.x - accP.x));
+}
+
+// dense fallback for the flagged pencils (after either sweep variant).  phase 0: everything; 1: only the gather of their
+// right-hand sides; 2: the rest (a sweep that emits M.X may overwrite a term of the right-hand side: gathered before it)
 template <int NF>
-static int finish_solve(PencilPack *pp, LuFactor *lu, const RhsSrc &rhs, double *x, hipStream_t s, int apply_p) {
+static int finish_solve(PencilPack *pp, LuFactor *lu, const RhsSrc &rhs, double *x, hipStream_t s, int apply_p, int phase = 0) {
     const PencilDev &P = pp->dev;
     const LuDev &d = lu->dev;
     if (lu->nflag) {
@@ -2814,12 +2908,15 @@ static int finish_solve(PencilPack *pp, LuFactor *lu, const RhsSrc &rhs, double 
         double2 *dx = drhs + (size_t)nsys * d.N;
         const long work = (long)lu->nflag * d.N * P.S;
         const unsigned gb = (unsigned)((work + 255) / 256);
-        hipLaunchKernelGGL(dense_gather_kernel<NF>, dim3(gb), dim3(256), 0, s, P, d, (const long *)lu->d_flag_cells,
-                           lu->nflag, rhs, drhs);
-        hipLaunchKernelGGL(dense_apply_kernel, dim3((unsigned)((d.N + 3) / 4), (unsigned)nsys), dim3(256), 0, s, d.N,
-                           (const double2 *)lu->d_inv, (const double2 *)drhs, dx);
-        hipLaunchKernelGGL(dense_scatter_kernel<NF>, dim3(gb), dim3(256), 0, s, P, d, (const long *)lu->d_flag_cells,
-                           lu->nflag, (const double2 *)dx, x, apply_p);
+        if (phase != 2)
+            hipLaunchKernelGGL(dense_gather_kernel<NF>, dim3(gb), dim3(256), 0, s, P, d, (const long *)lu->d_flag_cells,
+                               lu->nflag, rhs, drhs);
+        if (phase != 1) {
+            hipLaunchKernelGGL(dense_apply_kernel, dim3((unsigned)((d.N + 3) / 4), (unsigned)nsys), dim3(256), 0, s, d.N,
+                               (const double2 *)lu->d_inv, (const double2 *)drhs, dx);
+            hipLaunchKernelGGL(dense_scatter_kernel<NF>, dim3(gb), dim3(256), 0, s, P, d, (const long *)lu->d_flag_cells,
+                               lu->nflag, (const double2 *)dx, x, apply_p);
+        }
         DDH_HIP(hipGetLastError());
     }
     return 0;
@@ -2886,6 +2983,7 @@ struct SweepPlan {
     int bwd_w;                    // register window WT of the per-thread backward kernels (backward_window)
     int cb, tt;                   // cooperative backward sweep: lanes per system (CB) and entries per lane (TT)
     bool fuse_p;                  // x = P y fused into the backward sweep
+    bool emit_mx;                 // the backward sweep also writes M.x (MxEmit), no stand-alone mat-vec needed
     dim3 fwd_grid, fwd_block, bwd_grid, bwd_block;
     size_t lds_f, lds_b;
     // the lean forward sweep or its variants: all of them read tile-major terms and report as "lean"
@@ -2894,13 +2992,15 @@ struct SweepPlan {
 
 // nterms: right-hand-side terms of the solve; want_p: the caller asks for x = P y (the recombination fused into the
 // one-thread-per-system backward kernel of the real-graded 2-axis path, given a band table on file: LuDev::pband)
-static SweepPlan sweep_plan(const PencilPack *pp, const LuDev &d, int nterms, bool want_p) {
+// want_mx: the caller also asks for M.x from the backward sweep -- the full-size fused kernels with the 17-entry window only
+// (the deep, cooperative and block-inverse paths keep the stand-alone mat-vec)
+static SweepPlan sweep_plan(const PencilPack *pp, const LuDev &d, int nterms, bool want_p, bool want_mx = false) {
     const PencilDev &P = pp->dev;
     const int NF = P.nf, W = d.W;
     SweepPlan pl{};
     const size_t per_entry = d.pair ? 9 : 5;    // one (two when paired) int permutations + a code byte per row
     pl.lds_f = (size_t)(d.N + d.nb) * (per_entry + 1) + 16;          // (+ the zero-row flags of the lean sweep)
-    pl.lds_b = (size_t)(d.n > 0 ? d.n : 1) * (per_entry + 2) + 16;   // (+ the skip flags and the row-fill table of the backward sweep)
+    pl.lds_b = (size_t)(d.n > 0 ? d.n : 1) * (per_entry + 4) + 16;   // (+ the skip flags, the row-fill table and the M.X rows of the backward sweep)
     const unsigned blocks = (unsigned)((P.G + 255) / 256);
     // one thread per (system, block) where the sweep kernels support it (LuDev::nsplit)
     const long threads = (long)d.nsplit * d.Gp;
@@ -2986,6 +3086,9 @@ static SweepPlan sweep_plan(const PencilPack *pp, const LuDev &d, int nterms, bo
         } else {
             pl.bwd = BwdSweep::fused;
         }
+        // (the emitted rows are addressed with 32-bit byte offsets into the tile-major vector)
+        pl.emit_mx = want_mx && pl.bwd != BwdSweep::deep && pl.bwd_w == 17 && !(P.nx & 7) && !(P.ny & 7) &&
+                     (double)P.nrows * (double)P.nx * (double)P.ny * 8.0 < 4294967296.0;
     } else {
         pl.bwd = BwdSweep::plain;
         pl.bwd_w = backward_window(W);
@@ -2996,9 +3099,13 @@ static SweepPlan sweep_plan(const PencilPack *pp, const LuDev &d, int nterms, bo
 
 // (few window sizes: every instantiation is a fully unrolled kernel and this file dominates the build time)
 template <int NF>
-static int launch_solve(PencilPack *pp, LuFactor *lu, const RhsSrc &rhs, double *x, hipStream_t s, const SweepPlan &pl) {
+static int launch_solve(PencilPack *pp, LuFactor *lu, const RhsSrc &rhs, double *x, hipStream_t s, const SweepPlan &pl,
+                        int m_mat_id = -1, double *mx_out = nullptr) {
     const PencilDev &P = pp->dev;
     const LuDev &d = lu->dev;
+    const MxEmit mx{mx_out, (const double *)lu->d_mxband, (const short *)lu->d_mxrow};
+    const MxEmit nomx{nullptr, nullptr, nullptr};
+    if (pl.emit_mx && (!mx_out || !lu->mx_ok || m_mat_id < 0)) return fail("pencil_solve: M.X emission without its tables");
     if (pl.lds_f > 64 * 1024) return fail("pencil_solve: system too large for the LDS permutation cache");
     const int kl = pl.fwd_kl, nb = pl.fwd_nb, w = pl.bwd_w;
     switch (pl.fwd) {
@@ -3046,6 +3153,8 @@ static int launch_solve(PencilPack *pp, LuFactor *lu, const RhsSrc &rhs, double 
     if constexpr (NF > 0)
         if (pl.border_finish)
             hipLaunchKernelGGL(border_finish_kernel<NF>, dim3((unsigned)((P.G + 255) / 256)), dim3(256), 0, s, P, d, x);
+    if (pl.emit_mx)
+        if (int st = finish_solve<NF>(pp, lu, rhs, x, s, 0, 1)) return st;
     switch (pl.bwd) {
         case BwdSweep::none:
             break;
@@ -3064,14 +3173,19 @@ static int launch_solve(PencilPack *pp, LuFactor *lu, const RhsSrc &rhs, double 
                 hipLaunchKernelGGL((solve_backward_deep_kernel<17, 2>), pl.bwd_grid, pl.bwd_block, pl.lds_b, s, P, d, x, d.pband, rhs.skip);
             break;
         case BwdSweep::fused_occ4:
-            if constexpr (NF == 2)
-                hipLaunchKernelGGL((solve_backward_kernel<NF, 17, true, false, true, 4>), pl.bwd_grid, pl.bwd_block, pl.lds_b, s, P, d, x, d.pband, rhs.skip);
+            if constexpr (NF == 2) {
+                if (pl.emit_mx)
+                    hipLaunchKernelGGL((solve_backward_kernel<NF, 17, true, false, true, 4, true>), pl.bwd_grid, pl.bwd_block, pl.lds_b, s, P, d, x, d.pband, rhs.skip, mx);
+                else
+                    hipLaunchKernelGGL((solve_backward_kernel<NF, 17, true, false, true, 4>), pl.bwd_grid, pl.bwd_block, pl.lds_b, s, P, d, x, d.pband, rhs.skip, nomx);
+            }
             break;
         case BwdSweep::fused:
             if constexpr (NF == 2) {
                 auto k = w == 17 ? solve_backward_kernel<NF, 17, true, false, true> : w == 32 ? solve_backward_kernel<NF, 32, true, false, true>
                        : w == 34 ? solve_backward_kernel<NF, 34, true, false, true> : solve_backward_kernel<NF, 48, true, false, true>;
-                hipLaunchKernelGGL(k, pl.bwd_grid, pl.bwd_block, pl.lds_b, s, P, d, x, d.pband, rhs.skip);
+                if (pl.emit_mx) k = solve_backward_kernel<NF, 17, true, false, true, 1, true>;
+                hipLaunchKernelGGL(k, pl.bwd_grid, pl.bwd_block, pl.lds_b, s, P, d, x, d.pband, rhs.skip, pl.emit_mx ? mx : nomx);
             }
             break;
         case BwdSweep::plain: {
@@ -3082,12 +3196,23 @@ static int launch_solve(PencilPack *pp, LuFactor *lu, const RhsSrc &rhs, double 
                 k = w == 17 ? solve_backward_kernel<NF, 17, false, false> : w == 32 ? solve_backward_kernel<NF, 32, false, false>
                   : w == 34 ? solve_backward_kernel<NF, 34, false, false> : w == 48 ? solve_backward_kernel<NF, 48, false, false>
                   : solve_backward_kernel<NF, 64, false, false>;
-            hipLaunchKernelGGL(k, pl.bwd_grid, pl.bwd_block, pl.lds_b, s, P, d, x, d.pband, rhs.skip);
+            hipLaunchKernelGGL(k, pl.bwd_grid, pl.bwd_block, pl.lds_b, s, P, d, x, d.pband, rhs.skip, nomx);
             break;
         }
     }
     DDH_HIP(hipGetLastError());
-    return finish_solve<NF>(pp, lu, rhs, x, s, pl.fuse_p ? 1 : 0);
+    if (!pl.emit_mx) return finish_solve<NF>(pp, lu, rhs, x, s, pl.fuse_p ? 1 : 0);
+    if (int st = finish_solve<NF>(pp, lu, rhs, x, s, 1, 2)) return st;
+    if constexpr (NF == 2) {
+        if (lu->nflag) {
+            const MatDev &A = pp->mats[m_mat_id]->dev;
+            const long work = (long)A.nrows_out * lu->nflag;
+            hipLaunchKernelGGL(flagged_matvec_tiled_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, s, P, A,
+                               (const long *)lu->d_flag_cells, lu->nflag, (const double *)x, mx_out);
+            DDH_HIP(hipGetLastError());
+        }
+    }
+    return 0;
 }
 
 // Per-row upper width of the factors: wrow[j] = max over all factorizations of the last non-zero offset d of
@@ -3830,6 +3955,44 @@ static int build_pband(PencilPack *pp, LuFactor *lu, int p_mat_id) {
     return 0;
 }
 
+// Tables of the M.X emission (MxEmit), analysed by the host (dedalus_amd/core/solvers.py::mx_band_tables); checked here for
+// what the kernel's addressing relies on.
+int ddh_pencil_set_mx_band(ddh_handle pack, int lu_id, int m_mat_id, int width, const int *step_row_h, const double *band_h) {
+    PencilPack *pp = (PencilPack *)lookup_handle(pack, H_PENCIL);
+    if (!pp) return -1;
+    if (lu_id < 0 || lu_id >= (int)pp->lus.size()) return fail("pencil_set_mx_band: bad LU id");
+    if (m_mat_id < 0 || m_mat_id >= (int)pp->mats.size()) return fail("pencil_set_mx_band: bad matrix id");
+    LuFactor *lu = pp->lus[lu_id];
+    const LuDev &d = lu->dev;
+    lu->mx_ok = 0;
+    lu->mx_mat = -1;
+    const int n = d.n, nh = d.nsplit > 1 ? d.nh : d.n;
+    if (width != MXW || !step_row_h || !band_h) return fail("pencil_set_mx_band: tables of width 18");
+    if (!d.real || n <= 0 || n > 32767) return fail("pencil_set_mx_band: a real-graded factorization with 1 .. 32767 band rows");
+    if (pp->mats[m_mat_id]->dev.nrows_out != d.N) return fail("pencil_set_mx_band: matrix and factorization differ in size");
+    std::vector<char> seen(n, 0);
+    std::vector<short> step_row(n);
+    for (int t = 0; t < n; ++t) {
+        const int i = step_row_h[t];
+        if (i < -1 || i >= n) return fail("pencil_set_mx_band: equation row outside the band rows");
+        if (i >= 0 && seen[i]++) return fail("pencil_set_mx_band: an equation row formed twice");
+        step_row[t] = (short)i;
+        for (int dd = 0; dd < MXW; ++dd) {
+            const double v = band_h[(size_t)t * MXW + dd];
+            if (v == 0.0) continue;
+            if (!(v == v) || i < 0 || t + dd >= n || (t + dd) / nh != t / nh)
+                return fail("pencil_set_mx_band: an entry without a row, beyond the band rows or outside the block of its step");
+        }
+    }
+    if (!lu->d_mxband) DDH_HIP(hipMalloc(&lu->d_mxband, (size_t)n * MXW * sizeof(double) + 16));
+    if (!lu->d_mxrow) DDH_HIP(hipMalloc(&lu->d_mxrow, (size_t)n * sizeof(short) + 16));
+    DDH_HIP(hipMemcpy(lu->d_mxband, band_h, (size_t)n * MXW * sizeof(double), hipMemcpyHostToDevice));
+    DDH_HIP(hipMemcpy(lu->d_mxrow, step_row.data(), (size_t)n * sizeof(short), hipMemcpyHostToDevice));
+    lu->mx_mat = m_mat_id;
+    lu->mx_ok = 1;
+    return 0;
+}
+
 int ddh_pencil_solve_recombined(ddh_handle pack, int lu_id, int nterms, const double *const *xs_h,
                                 const double *alpha_h, int p_mat_id, double *work, double *x, void *stream) {
     return ddh_pencil_solve_recombined_sparse(pack, lu_id, nterms, xs_h, alpha_h, p_mat_id, work, x, nullptr, nullptr, stream);
@@ -3837,7 +4000,8 @@ int ddh_pencil_solve_recombined(ddh_handle pack, int lu_id, int nterms, const do
 
 static int solve_recombined_impl(ddh_handle pack, int lu_id, int nterms, const double *const *xs_h, const double *alpha_h,
                                  int p_mat_id, double *work, double *x, const unsigned char *zero_rows,
-                                 const unsigned char *skip_rows, int terms_tiled, void *stream);
+                                 const unsigned char *skip_rows, int terms_tiled, void *stream, int m_mat_id = -1,
+                                 double *mx_out = nullptr);
 
 int ddh_pencil_solve_recombined_sparse(ddh_handle pack, int lu_id, int nterms, const double *const *xs_h,
                                        const double *alpha_h, int p_mat_id, double *work, double *x,
@@ -3859,9 +4023,47 @@ int ddh_pencil_solve_recombined_tiled(ddh_handle pack, int lu_id, int nterms, co
     return solve_recombined_impl(pack, lu_id, nterms, xs_h, alpha_h, p_mat_id, work, x, zero_rows, skip_rows, 1, stream);
 }
 
+// whether the sweeps of a tiled recombined solve of this factorization emit M.x, whatever the number of right-hand-side terms
+static int mx_emission(PencilPack *pp, LuFactor *lu, int p_mat_id, bool *emits) {
+    *emits = false;
+    if (pp->dev.nf != 2 || p_mat_id < 0 || p_mat_id >= (int)pp->mats.size()) return 0;
+    if (int st = build_pband(pp, lu, p_mat_id)) return st;
+    for (int nterms = 1; nterms <= RHS_MAX; ++nterms)
+        if (!sweep_plan(pp, lu->dev, nterms, true, true).emit_mx || !sweep_plan(pp, lu->dev, nterms, false).lean_forward()) return 0;
+    *emits = true;
+    return 0;
+}
+
+int ddh_pencil_lu_emits_mx(ddh_handle pack, int lu_id, int p_mat_id, int *emits) {
+    PencilPack *pp = (PencilPack *)lookup_handle(pack, H_PENCIL);
+    if (!pp) return -1;
+    if (lu_id < 0 || lu_id >= (int)pp->lus.size() || !emits) return fail("pencil_lu_emits_mx: bad LU id");
+    bool e = false;
+    if (int st = mx_emission(pp, pp->lus[lu_id], p_mat_id, &e)) return st;
+    *emits = e ? 1 : 0;
+    return 0;
+}
+
+int ddh_pencil_solve_recombined_tiled_mx(ddh_handle pack, int lu_id, int nterms, const double *const *xs_h,
+                                         const double *alpha_h, int p_mat_id, double *work, double *x,
+                                         const unsigned char *zero_rows, const unsigned char *skip_rows, int m_mat_id,
+                                         double *mx_out, void *stream) {
+    PencilPack *pp = (PencilPack *)lookup_handle(pack, H_PENCIL);
+    if (!pp) return -1;
+    if (lu_id < 0 || lu_id >= (int)pp->lus.size()) return fail("pencil_solve: bad LU id");
+    if (!mx_out || mx_out == x || mx_out == work) return fail("pencil_solve_recombined_tiled_mx: M.x needs a vector of its own");
+    bool e = false;
+    if (int st = mx_emission(pp, pp->lus[lu_id], p_mat_id, &e)) return st;
+    if (!e || !pp->lus[lu_id]->mx_ok || pp->lus[lu_id]->mx_mat != m_mat_id)
+        return fail("pencil_solve_recombined_tiled_mx: the sweeps of this factorization do not emit M.x "
+                    "(ddh_pencil_lu_emits_mx) or have no tables for this matrix (ddh_pencil_set_mx_band)");
+    return solve_recombined_impl(pack, lu_id, nterms, xs_h, alpha_h, p_mat_id, work, x, zero_rows, skip_rows, 1, stream,
+                                 m_mat_id, mx_out);
+}
+
 static int solve_recombined_impl(ddh_handle pack, int lu_id, int nterms, const double *const *xs_h, const double *alpha_h,
                                  int p_mat_id, double *work, double *x, const unsigned char *zero_rows,
-                                 const unsigned char *skip_rows, int terms_tiled, void *stream) {
+                                 const unsigned char *skip_rows, int terms_tiled, void *stream, int m_mat_id, double *mx_out) {
     PencilPack *pp = (PencilPack *)lookup_handle(pack, H_PENCIL);
     if (!pp) return -1;
     if (lu_id < 0 || lu_id >= (int)pp->lus.size()) return fail("pencil_solve: bad LU id");
@@ -3884,8 +4086,8 @@ static int solve_recombined_impl(ddh_handle pack, int lu_id, int nterms, const d
     int st;
     if (pp->dev.nf == 2 && (st = build_pband(pp, lu, p_mat_id))) return st;
     // the fused kernel writes x directly; if the plan cannot fuse, the sweeps write the work vector instead
-    const SweepPlan pl = sweep_plan(pp, lu->dev, nterms, true);
-    if (pl.fuse_p) return launch_solve<2>(pp, lu, r, x, s, pl);
+    const SweepPlan pl = sweep_plan(pp, lu->dev, nterms, true, mx_out != nullptr);
+    if (pl.fuse_p) return launch_solve<2>(pp, lu, r, x, s, pl, m_mat_id, mx_out);
     r.skip = nullptr;       // (the unfused path recombines from `work` with a mat-vec: every row of it must be written)
     if (pp->dev.nf == 1 && lu->d_binv && lu->dev.real && lu->dev.n == lu->dev.nsplit * lu->dev.nh) {
         const LuDev &d = lu->dev;

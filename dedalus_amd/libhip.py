@@ -135,6 +135,9 @@ SIGNATURES = {
     "ddh_pencil_solve_recombined": [_h, _i, _i, C.POINTER(_vp), _dp, _i, _vp, _vp, _vp],
     "ddh_pencil_solve_recombined_sparse": [_h, _i, _i, C.POINTER(_vp), _dp, _i, _vp, _vp, _vp, _vp, _vp],
     "ddh_pencil_solve_recombined_tiled": [_h, _i, _i, C.POINTER(_vp), _dp, _i, _vp, _vp, _vp, _vp, _vp],
+    "ddh_pencil_solve_recombined_tiled_mx": [_h, _i, _i, C.POINTER(_vp), _dp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp],
+    "ddh_pencil_lu_emits_mx": [_h, _i, _i, _ip],
+    "ddh_pencil_set_mx_band": [_h, _i, _i, _i, _ip, _dp],
     "ddh_pencil_matvec_update_tiled": [_h, _i, _vp, _vp, _vp],
     "ddh_pencil_flagged": [_h, _i, _ip, C.POINTER(_l), _i],
     "ddh_pencil_set_dense_inverse": [_h, _i, _dp],

@@ -301,12 +301,24 @@ class PencilPack:
 
     supports_zero_rows = True
 
-    def solve_recombined(self, lu_id, xs, alphas, p_mat_id, work, x, zero_rows=None, skip_rows=None, tiled=False):
+    def solve_recombined(self, lu_id, xs, alphas, p_mat_id, work, x, zero_rows=None, skip_rows=None, tiled=False, mx=None):
         """x = P (a M + b L P)^-1 (sum_t alphas[t] xs[t]) (ddh_pencil_solve_recombined): recombination fused into the
         backward sweep where the kernel variant allows, else through `work` and a mat-vec.
         zero_rows = (device uint8 mask, fraction set): rows that are zero in every term; skip_rows = (mask, fraction):
-        unknowns the caller does not need (ddh_pencil_solve_recombined_sparse)."""
+        unknowns the caller does not need (ddh_pencil_solve_recombined_sparse).
+        mx = (mass matrix id, tile-major destination): the backward sweep also writes M x there
+        (ddh_pencil_solve_recombined_tiled_mx; only where `emits_mx` says so, with tiled terms)."""
         t = self._timer()
+        if t is not None and mx is not None:
+            # the factors, the terms and x as below, plus the rows of M.x the sweep writes
+            info = self.lu_info(lu_id)
+            read = 1.0 - (zero_rows[1] if (zero_rows is not None and info["forward"] == "lean") else 0.0)
+            wrote = 1.0 - (skip_rows[1] if skip_rows is not None else 0.0)
+            mrows = len(np.unique(np.asarray(self.matrices[mx[0]].row)))
+            nb = self.lu_bytes(lu_id) + (sum(v.numel() for v in xs) * read + x.numel() * wrote
+                                         + mx[1].numel() * mrows / float(self.nrows)) * 8
+            return t.run("pencil_solve", nb, self._solve_recombined, lu_id, xs, alphas, p_mat_id, work, x, zero_rows,
+                         skip_rows, tiled, mx)
         if t is not None:
             info = self.lu_info(lu_id)          # masked rows are not read / written -- by the kernels that honour the masks
             read = 1.0 - (zero_rows[1] if (zero_rows is not None and info["forward"] == "lean") else 0.0)
@@ -317,14 +329,20 @@ class PencilPack:
                 nb = binv + (sum(v.numel() for v in xs) + 3 * x.numel()) * 8      # (+ work written, read by the P mat-vec, x written)
             return t.run("pencil_solve", nb, self._solve_recombined, lu_id, xs, alphas, p_mat_id, work, x, zero_rows,
                          skip_rows, tiled)
-        return self._solve_recombined(lu_id, xs, alphas, p_mat_id, work, x, zero_rows, skip_rows, tiled)
+        return self._solve_recombined(lu_id, xs, alphas, p_mat_id, work, x, zero_rows, skip_rows, tiled, mx)
 
-    def _solve_recombined(self, lu_id, xs, alphas, p_mat_id, work, x, zero_rows=None, skip_rows=None, tiled=False):
+    def _solve_recombined(self, lu_id, xs, alphas, p_mat_id, work, x, zero_rows=None, skip_rows=None, tiled=False, mx=None):
         arr = (C.c_void_p * len(xs))(*[C.c_void_p(v.data_ptr()) for v in xs])
         al = np.ascontiguousarray(alphas, dtype=np.float64)
         if zero_rows is not None or skip_rows is not None or tiled:
             zp = C.c_void_p(zero_rows[0].data_ptr()) if zero_rows is not None else None
             sp = C.c_void_p(skip_rows[0].data_ptr()) if skip_rows is not None else None
+            if mx is not None:
+                if not tiled:
+                    raise ValueError("M.x from the sweep needs tile-major terms")
+                libhip.call("ddh_pencil_solve_recombined_tiled_mx", self.handle, lu_id, len(xs), arr, libhip.as_dp(al),
+                            int(p_mat_id), ptr(work), ptr(x), zp, sp, int(mx[0]), ptr(mx[1]), self.dev.stream)
+                return
             libhip.call("ddh_pencil_solve_recombined_tiled" if tiled else "ddh_pencil_solve_recombined_sparse", self.handle,
                         lu_id, len(xs), arr, libhip.as_dp(al), int(p_mat_id), ptr(work), ptr(x), zp, sp, self.dev.stream)
             return
@@ -361,6 +379,22 @@ class PencilPack:
         d = dict(zip(keys, (int(x) for x in v)))
         d["forward"] = ("general", "lean", "cooperative")[d["forward"]]
         return d
+
+    def emits_mx(self, lu_id, p_mat_id):
+        """Whether the sweeps of a tiled recombined solve of this factorization can write M x (ddh_pencil_lu_emits_mx:
+        the kernels only; the tables come from `set_mx_band`); depends on the sweep variant, like lu_info."""
+        if not hasattr(libhip.load(), "ddh_pencil_lu_emits_mx"):
+            return False                    # (DDH_LIB: an older build of the library, for A/B timing)
+        v = C.c_int(0)
+        libhip.call("ddh_pencil_lu_emits_mx", self.handle, int(lu_id), int(p_mat_id), C.byref(v))
+        return bool(v.value)
+
+    def set_mx_band(self, lu_id, m_mat_id, step_row, band):
+        """Tables of the M x emission for mass matrix m_mat_id (ddh_pencil_set_mx_band; core/solvers.py::mx_band_tables)."""
+        sr = np.ascontiguousarray(step_row, dtype=np.int32)
+        bd = np.ascontiguousarray(band, dtype=np.float64)
+        libhip.call("ddh_pencil_set_mx_band", self.handle, int(lu_id), int(m_mat_id), int(bd.shape[1]), libhip.as_ip(sr),
+                    libhip.as_dp(bd))
 
     def lu_bytes(self, lu_id):
         n = C.c_size_t(0)

@@ -542,6 +542,36 @@ int ddh_pencil_matvec_update_tiled(ddh_handle pack, int mat_id, const double *x,
 int ddh_pencil_solve_recombined_tiled(ddh_handle pack, int lu_id, int nterms, const double *const *xs_h,
                                       const double *alpha_h, int p_mat_id, double *work, double *x,
                                       const unsigned char *zero_rows, const unsigned char *skip_rows, void *stream);
+/* M.x from the backward sweep.  A Runge-Kutta step needs M.X of the state a solve has just written (the next stage's
+ * right-hand side, core/timesteppers.py:588-604): ddh_pencil_matvec_update_tiled reads that state back from HBM.  With
+ * the recombination fused, the one-thread-per-system backward sweep holds y_j .. y_(j+17) of x = P y in registers when row j
+ * is done, and every row of the band of M P (M real and wavenumber independent: conversions between polynomial bases) fits
+ * that window: the full-size sweep writes (M x)[row] = sum_d (M P)[row, j + d] y_(j+d) itself, tile-major, into mx_out.
+ *   ddh_pencil_solve_recombined_tiled_mx  ddh_pencil_solve_recombined_tiled + mx_out = M x for the matrix m_mat_id (the
+ *                                         physical mass matrix; with partner pencils it must share their symmetry).  Rows
+ *                                         of M without terms are not written (mx_out is a persistent, zeroed buffer, as for
+ *                                         ddh_pencil_matvec_update*); unknowns masked by skip_rows still enter the product;
+ *                                         flagged pencils get theirs from their dense solution.  mx_out may be one of the
+ *                                         right-hand-side terms (they are consumed before the backward sweep).  An error
+ *                                         when the sweeps of the factorization do not emit:
+ *   ddh_pencil_lu_emits_mx                *emits = 1 when the kernels can, for any number of right-hand-side terms --
+ *                                         the lean forward sweep and the one-thread-per-(system, block) backward sweep
+ *                                         with the fused recombination and a window of 17 (not the deep, cooperative or
+ *                                         block-inverse paths), tile-able sizes.  Depends on ddh_pencil_set_solve_variant.
+ *   ddh_pencil_set_mx_band                the host's analysis of M P in the ordering of the factorization (the caller has
+ *                                         the graded term lists; with partner pencils M P must share their symmetry):
+ *                                         step_row_h[j] (n ints) = the logical equation row formed when row j of the
+ *                                         sweep is done, -1 none; band_h[j * width + d] = (M P)[step_row_h[j], j + d],
+ *                                         width = 18.  Checked here: every row at most once, no entry beyond the band
+ *                                         rows or outside the diagonal block of its step.  Needed before the solve.
+ * The reference forms M.X with a sparse product per subproblem (core/timesteppers.py:588-604); the values agree to the
+ * round-off of a different summation order.                                                                            */
+int ddh_pencil_solve_recombined_tiled_mx(ddh_handle pack, int lu_id, int nterms, const double *const *xs_h,
+                                         const double *alpha_h, int p_mat_id, double *work, double *x,
+                                         const unsigned char *zero_rows, const unsigned char *skip_rows, int m_mat_id,
+                                         double *mx_out, void *stream);
+int ddh_pencil_lu_emits_mx(ddh_handle pack, int lu_id, int p_mat_id, int *emits);
+int ddh_pencil_set_mx_band(ddh_handle pack, int lu_id, int m_mat_id, int width, const int *step_row_h, const double *band_h);
 /* Independent diagonal blocks.  When the band block of the ordered pencil matrix (rows / columns < n_interior of
  * ddh_pencil_factor*) is block diagonal with `nblocks` blocks of EQUAL size -- the connected components of the matrix,
  * e.g. the two reflection parities of constant-coefficient equations between two plates once the boundary rows are
