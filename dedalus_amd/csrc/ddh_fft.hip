@@ -1482,6 +1482,32 @@ int ddh_rfft_bilinear_fused(ddh_handle plan, int na, const double *const *a_h, c
     return 0;
 }
 
+int ddh_rfft_fused_plan_info(int n_grid, int n_coeff, long nlines, int *info) {
+    if (!info) return fail("ddh_rfft_fused_plan_info: null pointer");
+    if (n_grid < 1 || n_coeff < 2 || (n_coeff & 1) || nlines < 1)
+        return fail("ddh_rfft_fused_plan_info: n_grid >= 1, even n_coeff >= 2, nlines >= 1");
+    // the fields of a real-Fourier plan's descriptor that fused_plan reads (make_plan), without the plan
+    FftDev d;
+    memset(&d, 0, sizeof(d));
+    d.N = n_grid;
+    d.M = n_coeff;
+    d.K = fourier_kmax(n_grid, n_coeff);
+    d.ld = n_grid + (n_grid >> 4) + 1;
+    const FusedPlan fp = fused_plan(d, nlines);
+    if (fp.error) return fail(fp.error);
+    const bool wave = fp.kernel != FusedKernel::workgroup;
+    info[0] = fp.N;
+    info[1] = fp.kernel == FusedKernel::gridwave2 ? 0 : fp.kernel == FusedKernel::gridwave ? 1 : 2;
+    info[2] = wave ? fp.C : 0;
+    info[3] = wave ? fp.NT : 0;
+    info[4] = wave && fp.twreg ? 1 : 0;
+    info[5] = wave && fp.dma ? 1 : 0;
+    info[6] = wave ? (int)fp.lpw : 0;
+    info[7] = (int)fp.grid;
+    info[8] = (int)fp.block;
+    return 0;
+}
+
 int ddh_plan_mmt(ddh_handle *plan, int n_out, int n_in, const double *mat_h) {
     if (n_out < 1 || n_in < 1) return fail("plan_mmt: sizes must be positive");
     MmtPlan *pl = new MmtPlan();

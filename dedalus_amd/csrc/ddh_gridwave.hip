@@ -454,19 +454,20 @@ FusedPlan fused_plan(const FftDev &d, long nlines) {
     FusedPlan fp{};
     // A WIDER INTERNAL GRID where this grid size has no wave kernel (round 6).  The stage maps coefficient lines to
     // coefficient lines; its grid never reaches memory.  Bilinear products of lines with modes <= K are free of aliasing in
-    // the retained modes on ANY grid of N' > 3 K points, so the stage may run on the smallest N' >= N the wave kernels are
-    // instantiated for (N' = 128 C) and returns the same coefficients up to round-off -- e.g. 192-point lines (128 modes) on
-    // 256 points, 576-point lines (384 modes) on 768 -- instead of the workgroup-per-line-pair kernel (0.05-0.12 of the HBM
-    // rate, profiles/r6_offsize_configs.txt).
-    // TODO (first item): an under-dealiased plan (N <= 3 K) is widened too, which removes the aliasing the
-    // caller's own grid would have produced.
+    // the retained modes on ANY grid of N' > 3 K points.  So where the plan's own grid is such a grid (N > 3 K), the stage
+    // may run on the smallest N' >= N the wave kernels are instantiated for (N' = 128 C) and returns the same coefficients
+    // up to round-off -- e.g. 192-point lines (128 modes) on 256 points, 576-point lines (384 modes) on 768 -- instead of
+    // the workgroup-per-line-pair kernel (0.05-0.12 of the HBM rate, profiles/r6_offsize_configs.txt).  An under-dealiased
+    // plan (N <= 3 K: dealias = 1, or any ratio below 3/2) keeps its own size and whatever kernel that has: its products
+    // alias on the N-point grid, the reference and the unfused path keep that aliasing, and a wider grid would remove it.
     const int sizes[] = {d.N, 256, 384, 512, 768, 1024};
     size_t lds1 = 0, lds2 = 0;
     bool wave = false;
     fp.N = d.N;
+    const bool alias_free = d.N > 3 * d.K;
     for (int i = 0; i < 6 && !wave && !old; ++i) {
         const int Np = sizes[i];
-        if (i > 0 && !(wider && Np >= d.N && Np > 3 * d.K)) continue;
+        if (i > 0 && !(wider && alias_free && Np >= d.N && Np > 3 * d.K)) continue;
         if (gridwave_supported(Np, d.M, lds1, lds2)) {
             fp.N = Np;
             wave = true;

@@ -92,6 +92,7 @@ SIGNATURES = {
     "ddh_cheb_backward_dual": [_h, _vp, _vp, _vp, _vp, _l, _l, _vp],
     "ddh_rfft_bilinear_fused": [_h, _i, C.POINTER(_vp), _dp, _i, C.POINTER(_vp), _dp, _i, C.POINTER(_vp), _l, _i,
                                 _ip, _ip, _ip, _dp, _vp],
+    "ddh_rfft_fused_plan_info": [_i, _i, _l, _ip],
     "ddh_plan_cfft": [_hp, _i, _i],
     "ddh_cfft_forward": [_h, _vp, _vp, _l, _l, _vp],
     "ddh_cfft_backward": [_h, _vp, _vp, _l, _l, _vp],

@@ -88,6 +88,16 @@ int ddh_rfft_bilinear_fused(ddh_handle plan, int na, const double *const *a_h, c
                             int nb, const double *const *b_h, const double *b_dscale_h, int nc,
                             double *const *out_h, long nlines, int nterms, const int *ic_h,
                             const int *ia_h, const int *ib_h, const double *coef_h, void *stream);
+/* Diagnostic: which kernel a ddh_rfft_bilinear_fused call of nlines lines takes on a plan of n_grid points / n_coeff
+ * coefficients, without a plan or a device (nothing is launched or allocated).  info[9]:
+ *   [0] internal grid size: n_grid, or the wider size the stage works on where n_grid has no wave kernel and the plan's
+ *       own grid is already free of aliasing (n_grid > 3 kmax), so that the wider grid returns the same coefficients
+ *   [1] kernel family: 0 wave-per-line second generation, 1 wave-per-line first generation, 2 workgroup-per-line-pair
+ *   [2] C (internal grid = 128 C)   [3] NT (64-pair blocks loaded per line)   [4] twiddles in registers
+ *   [5] operands by LDS-DMA         [6] lines per wave     ([2]..[6] are 0 for the workgroup kernel)
+ *   [7] workgroups                  [8] threads per workgroup
+ * Tests assert the selection of a size with it, so that a fallback to another kernel fails them.                       */
+int ddh_rfft_fused_plan_info(int n_grid, int n_coeff, long nlines, int *info);
 
 /* Chebyshev-T grid (a0=b0=-1/2) with optional ultraspherical output basis: replaces
  * FFTWFastChebyshevTransform core/transforms.py:801-902 (FastCosineTransform :715-746, FFTWDCT
