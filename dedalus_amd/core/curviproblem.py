@@ -1,22 +1,34 @@
 """
 Problem front end shared by the sphere (core/sphere.py) and the shell (core/shell.py): the namespace, equation parsing
-and the split of a linear LHS into dt-terms (M) and the rest (L), {variable index: term list} each.  A geometry declares
-its operand classes and operator names and the few places where the two really differ.
+and the split of a linear LHS into dt-terms (M) and the rest (L), {variable index: term list} each.  The expression
+nodes it walks are those of core/curvioperand.py; a geometry declares its operand base class and operator names and the
+few places where the two really differ.
 """
 
 import numbers
 
 import numpy as np
 
+from .curvioperand import NonlinearError
 from .problems import _split_equation
 
 
-class NonlinearError(ValueError):
-    """raised by an operand's lin(): it is not linear in the problem variables"""
+class MatvecPack:
+    """matvec interface the shared timesteppers use (pack.matvec(id, x, y)) over device term lists"""
+
+    def __init__(self):
+        self.mats = []
+
+    def add(self, dev_terms):
+        self.mats.append(dev_terms)
+        return len(self.mats) - 1
+
+    def matvec(self, mid, x, y):
+        self.mats[mid].apply(x, y)
 
 
 class CurvilinearProblem:
-    operand_type = add_type = scale_type = None      # the geometry's operand base class and its sum / scaling nodes
+    operand_type = None                              # the geometry's operand base class (core/curvioperand.py)
     operators = {}                                   # names the equations may use
 
     def __init__(self, variables, namespace=None, time="t"):
@@ -32,8 +44,8 @@ class CurvilinearProblem:
 
     # ---- what differs between the geometries -------------------------------------------------------------------------
     def _lin(self, node):
-        """node.lin(...) with the geometry's arguments"""
-        raise NotImplementedError
+        """({variable index: term list}, is it a dt term) of one term of a left-hand side"""
+        return node.lin(self.variables)
 
     def _numeric_rhs(self, rhs):
         """F of a right-hand side that is a number"""
@@ -80,10 +92,10 @@ class CurvilinearProblem:
         terms = []
 
         def flatten(node, scale):
-            if isinstance(node, self.add_type):
+            if isinstance(node, self.operand_type.add_type):
                 for a in node.args:
                     flatten(a, scale)
-            elif isinstance(node, self.scale_type):
+            elif isinstance(node, self.operand_type.scale_type):
                 flatten(node.arg, scale * node.a)
             else:
                 terms.append((scale, node))

@@ -24,7 +24,8 @@ from ..tools import sphere as sph
 from . import curvilinear, sphreduce
 from .basis import Jacobi
 from .coords import Coordinate, SpinCoordinates
-from .curviproblem import CurvilinearProblem, NonlinearError
+from .curvioperand import Add, CurviOperand, Dt, NonlinearError, Scale, bilinear_terms
+from .curviproblem import CurvilinearProblem, MatvecPack
 from .ivp_common import LUSlotSolver
 from .mirror import HostMirror
 from .sphere import S2Coordinates, SphereBasis
@@ -770,9 +771,9 @@ def operate_slot_sequences(sb):
     return sb._plans[key]
 
 
-class ShOperand:
-    """Expression node in spherical coordinates.  basis: ShellBasis (k), SurfaceBasis or None."""
-    __array_priority__ = 100.0
+class ShOperand(CurviOperand):
+    """Expression node in spherical coordinates (the algebra: core/curvioperand.py).  basis: ShellBasis (k), SurfaceBasis
+    or None."""
 
     def __array_ufunc__(self, ufunc, method, *inputs, **kw):
         """numpy scalars and ufuncs applied to operands (np.sqrt(u@u), np.float64(2) * u, ...)"""
@@ -802,42 +803,12 @@ class ShOperand:
     def ncomp(self):
         return int(np.prod(self.sig, dtype=np.int64))
 
-    def __add__(self, other):
-        return ShAdd.make(self, other)
-
-    __radd__ = __add__
-
-    def __sub__(self, other):
-        return ShAdd.make(self, -1 * other if isinstance(other, ShOperand) else -other)
-
-    def __rsub__(self, other):
-        return ShAdd.make(-1 * self, other)
-
-    def __neg__(self):
-        return ShScale(-1.0, self)
-
-    def __mul__(self, other):
-        if isinstance(other, numbers.Number):
-            return ShScale(other, self)
-        if isinstance(other, ShOperand):
-            return ShProduct(self, other)
-        return NotImplemented
-
-    def __rmul__(self, other):
-        if isinstance(other, numbers.Number):
-            return ShScale(other, self)
-        return NotImplemented
-
-    def __matmul__(self, other):
-        return ShProduct(self, other, contract=True)
+    @staticmethod
+    def dot(a, b):
+        return ShProduct(a, b, contract=True)
 
     def eval_g(self):
         return _eval_grid(self)
-
-    def __truediv__(self, other):
-        if isinstance(other, numbers.Number):
-            return ShScale(1.0 / other, self)
-        return NotImplemented
 
     def __call__(self, **kw):
         """T(r=Ri): interpolation along the radius (core/operators.py interpolate dispatch)."""
@@ -852,9 +823,6 @@ class ShOperand:
             return ShUnsupported("interpolation along %r" % name, self)
         return ShLinear("interp", self, position=float(pos))
 
-    def has_dt(self):
-        return any(a.has_dt() for a in getattr(self, "args", ()) if isinstance(a, ShOperand))
-
     def grid_native(self):
         """Grid data when the operand is formed in grid space (products), else None."""
         return None
@@ -863,10 +831,8 @@ class ShOperand:
         """True when grid_native() gives data (asked before evaluating anything)"""
         return False
 
-    def evaluate(self):
-        f = ShellField(self.dist, self.basis, rank=self.rank, sig=self.sig)
-        f._set_device_coeff(self.eval_c())
-        return f
+    def _result_field(self):
+        return ShellField(self.dist, self.basis, rank=self.rank, sig=self.sig)
 
 
 def _no_s2_index(what, *args):
@@ -887,8 +853,7 @@ class ShReduced(sphreduce.ReducedResult, ShOperand):
             raise NotImplementedError("%s of an operand without an angular basis" % self.what)
         _no_s2_index(self.what, arg)
         if isinstance(arg, ShLinear) and arg.kind in ("interp", "integ"):
-            raise NotImplementedError("%s of a reduced operand (%s): reductions of reductions are not supported"
-                                      % (self.what, arg.kind))
+            raise sphreduce.reduction_refused(self.what, arg.kind)
         self._init(arg, **params)
 
     @property
@@ -914,9 +879,6 @@ class ShReduced(sphreduce.ReducedResult, ShOperand):
         if self.dist.size > 1:
             raise NotImplementedError("%s on several ranks: the azimuthal wavenumbers are distributed where it is formed"
                                       % self.what)
-
-    def lin(self, variables):
-        raise NonlinearError("%s in an equation" % self.what)
 
 
 class ShAzimuthalInterp(ShReduced):
@@ -1104,10 +1066,10 @@ class ShUnary(ShOperand):
         raise NonlinearError("grid functions are nonlinear")
 
 
-class ShScale(ShOperand):
+class ShScale(Scale, ShOperand):
     def __init__(self, a, arg):
-        self.a, self.arg, self.args = float(a), arg, (arg,)
-        self.dist, self.basis, self.rank, self._sig = arg.dist, arg.basis, arg.rank, arg.sig
+        Scale.__init__(self, a, arg)
+        self._sig = arg.sig
 
     def is_grid_native(self):
         return self.arg.is_grid_native()
@@ -1120,17 +1082,6 @@ class ShScale(ShOperand):
         out = ex.empty(tuple(g.shape))
         ex.lincomb(out, [g], [self.a])
         return out
-
-    def eval_c(self):
-        ex = self.dist.executor
-        c = self.arg.eval_c()
-        out = ex.empty(tuple(c.shape))
-        ex.lincomb(out, [c], [self.a])
-        return out
-
-    def lin(self, variables):
-        d, dt = self.arg.lin(variables)
-        return {i: t.scaled(self.a) for i, t in d.items()}, dt
 
 
 def _common_basis(a, b):
@@ -1154,22 +1105,14 @@ def _converted(x, basis):
     return x
 
 
-class ShAdd(ShOperand):
-    @staticmethod
-    def make(a, b):
-        for x, y in ((a, b), (b, a)):
-            if isinstance(x, numbers.Number):
-                if x == 0:
-                    return y
-                raise NotImplementedError("adding a number to a shell field")
-        return ShAdd(a, b)
+class ShAdd(Add, ShOperand):
+    geometry = "shell"
 
     def __init__(self, a, b):
-        if a.rank != b.rank:
-            raise ValueError("cannot add tensors of different rank")
+        Add.__init__(self, a, b)
         if a.sig != b.sig:
             raise ValueError("cannot add tensors of different signature: components per index %s and %s" % (a.sig, b.sig))
-        self.dist, self.rank, self._sig = a.dist, a.rank, a.sig
+        self._sig = a.sig
         self.basis = _common_basis(a, b)
         self.args = (_converted(a, self.basis), _converted(b, self.basis))
 
@@ -1199,18 +1142,6 @@ class ShAdd(ShOperand):
 
     def eval_g(self):
         return self.grid_native() if self.is_grid_native() else _eval_grid(self)
-
-    def lin(self, variables):
-        out, anydt = {}, None
-        for x in self.args:
-            d, dt = x.lin(variables)
-            if anydt is None:
-                anydt = dt
-            elif anydt != dt:
-                raise NonlinearError("dt and non-dt terms inside one sum node")
-            for i, t in d.items():
-                out[i] = out[i] + t if i in out else t
-        return out, bool(anydt)
 
 
 class ShLinear(ShOperand):
@@ -1318,22 +1249,8 @@ class ShLinear(ShOperand):
         return {i: tl.compose(t) for i, t in d.items()}, dt
 
 
-class ShDt(ShOperand):
-    def __init__(self, arg):
-        self.arg, self.args = arg, (arg,)
-        self.dist, self.basis, self.rank = arg.dist, arg.basis, arg.rank
-
-    def has_dt(self):
-        return True
-
-    def lin(self, variables):
-        d, dt = self.arg.lin(variables)
-        if dt:
-            raise NonlinearError("nested time derivatives")
-        return d, True
-
-    def eval_c(self):
-        raise ValueError("dt() cannot be evaluated")
+class ShDt(Dt, ShOperand):
+    pass
 
 
 def _padded(ex, c, Nr):
@@ -1392,7 +1309,7 @@ class ShProduct(ShOperand):
         Nt = self.dist.theta_range(Nt)[1]
         ga = a.grid_broadcast(ex, self.basis, (Np, Nt, Ng)) if isinstance(a, RadialField) else a.eval_g()
         gb = b.grid_broadcast(ex, self.basis, (Np, Nt, Ng)) if isinstance(b, RadialField) else b.eval_g()
-        terms, nout = (CROSS_TERMS, 3) if self.cross else _bilinear_terms3(a.rank, b.rank, self.contract)
+        terms, nout = (CROSS_TERMS, 3) if self.cross else bilinear_terms(3, a.rank, b.rank, self.contract)
         out = ex.empty((nout, Np, Nt, Ng))
         ex.bilinear(out, nout, ga, gb, Np * Nt * Ng, terms)
         return out
@@ -1428,21 +1345,7 @@ class ShProduct(ShOperand):
 CROSS_TERMS = [(0, 2, 1, 1.0), (0, 1, 2, -1.0), (1, 0, 2, 1.0), (1, 2, 0, -1.0), (2, 1, 0, 1.0), (2, 0, 1, -1.0)]
 
 
-def _bilinear_terms3(rank_a, rank_b, contract):
-    ia_list = list(np.ndindex(*((3,) * rank_a)))
-    ib_list = list(np.ndindex(*((3,) * rank_b)))
-    out_list = list(np.ndindex(*((3,) * (rank_a + rank_b - (2 if contract else 0)))))
-    terms = []
-    for ia, ta in enumerate(ia_list):
-        for ib, tb in enumerate(ib_list):
-            if contract:
-                if ta[-1] != tb[0]:
-                    continue
-                tc = tuple(ta[:-1]) + tuple(tb[1:])
-            else:
-                tc = tuple(ta) + tuple(tb)
-            terms.append((out_list.index(tc), ia, ib, 1.0))
-    return terms, len(out_list)
+ShOperand.scale_type, ShOperand.add_type, ShOperand.product = ShScale, ShAdd, ShProduct
 
 
 def ncc_termlist(ncc, arg_basis, rank_arg, ncc_first, contract):
@@ -1517,7 +1420,7 @@ def ave(a, *coords):
         coords = tuple(coords[0])
     cs = a.dist.coordsys
     if isinstance(a, ShReduced):
-        raise NotImplementedError("average of a reduced operand (%s): reductions of reductions are not supported" % a.what)
+        raise sphreduce.reduction_refused("average", a.what)
     if not coords:
         return ShSphereAverage(a)
     names = [c if isinstance(c, str) else getattr(c, "name", None) for c in coords]
@@ -2139,7 +2042,7 @@ class ShellField(HostMirror, ShOperand):
 # ==================================================================================================
 
 class ShellProblem(CurvilinearProblem):
-    operand_type, add_type, scale_type = ShOperand, ShAdd, ShScale
+    operand_type = ShOperand
     operators = dict(lap=lap, grad=grad, div=div, dt=dt, Lift=Lift, lift=Lift, trace=trace, integ=integ,
                      Laplacian=lap, Gradient=grad, Divergence=div, TimeDerivative=dt, Trace=trace,
                      Integrate=integ, ave=ave, Average=ave, curl=curl, Curl=curl, cross=cross, CrossProduct=cross,
@@ -2179,18 +2082,6 @@ class ShellLBVP(ShellProblem):
     @property
     def solver_class(self):
         return ShellBoundaryValueSolver
-
-
-class _EllPack:
-    def __init__(self):
-        self.mats = []
-
-    def add(self, dev):
-        self.mats.append(dev)
-        return len(self.mats) - 1
-
-    def matvec(self, mid, x, y):
-        self.mats[mid].apply(x, y)
 
 
 def _valid_modes(basis, sig, nl, Nr):
@@ -2237,7 +2128,7 @@ class ShellSolverBase:
         self.row_valid = self._packed_valid([(eq["basis"], eq["lhs"].sig) for eq in problem.equations], self.emap)
         self.M_tl = self._system_termlist("M")
         self.L_tl = self._system_termlist("L")
-        self.pack = _EllPack()
+        self.pack = MatvecPack()
         self.cx = self.M_tl.rotated or self.L_tl.rotated          # complex per-ell systems on (cos, msin) pairs
         self._assert_real_ell0()
         mk = lambda tl: self.ex.make_ell_terms(self.nm, self.nl, self.Nr, self.R, tl.terms,

@@ -35,7 +35,8 @@ from ..tools import jacobi
 from ..tools import sphere as sph
 from . import sphreduce
 from .coords import Coordinate, SpinCoordinates
-from .curviproblem import CurvilinearProblem, NonlinearError
+from .curvioperand import Add, CurviOperand, Dt, NonlinearError, Scale, bilinear_terms
+from .curviproblem import CurvilinearProblem, MatvecPack
 from .ivp_common import LUSlotSolver
 from .mirror import HostMirror
 
@@ -463,47 +464,13 @@ def op_termlist(kind, basis, rank_in, **kw):
 # operands
 # ==================================================================================================
 
-class SOperand:
-    """Expression node on the sphere.  rank = tensor rank (components over S2), basis may be None (constant)."""
-    __array_priority__ = 100.0
+class SOperand(CurviOperand):
+    """Expression node on the sphere (the algebra: core/curvioperand.py).  rank = tensor rank (components over S2), basis
+    may be None (constant)."""
     __array_ufunc__ = None          # numpy scalars defer to __rmul__ / __radd__
-
-    def __add__(self, other):
-        return SAdd.make(self, other)
-
-    __radd__ = __add__
-
-    def __sub__(self, other):
-        return SAdd.make(self, -1 * other if isinstance(other, SOperand) else -other)
-
-    def __rsub__(self, other):
-        return SAdd.make(-1 * self, other)
-
-    def __neg__(self):
-        return SScale(-1.0, self)
 
     def __pos__(self):
         return self
-
-    def __mul__(self, other):
-        if isinstance(other, numbers.Number):
-            return SScale(other, self)
-        if isinstance(other, SOperand):
-            return SProduct(self, other)
-        return NotImplemented
-
-    def __rmul__(self, other):
-        if isinstance(other, numbers.Number):
-            return SScale(other, self)
-        return NotImplemented
-
-    def __truediv__(self, other):
-        if isinstance(other, numbers.Number):
-            return SScale(1.0 / other, self)
-        return NotImplemented
-
-    def __matmul__(self, other):
-        return SDot(self, other)
 
     def __call__(self, **kw):
         """f(phi=phi0), f(theta=theta0): interpolation along one coordinate (output tasks)."""
@@ -521,13 +488,8 @@ class SOperand:
     def ncomp(self):
         return 2 ** self.rank
 
-    def evaluate(self):
-        f = SField(self.dist, basis=self.basis, rank=self.rank)
-        f._set_device_coeff(self.eval_c())
-        return f
-
-    def has_dt(self):
-        return any(a.has_dt() for a in getattr(self, "args", ()) if isinstance(a, SOperand))
+    def _result_field(self):
+        return SField(self.dist, basis=self.basis, rank=self.rank)
 
     # evaluation to device arrays ------------------------------------------------------------------------------
     def eval_c(self):
@@ -540,13 +502,9 @@ class SOperand:
         return _backward(self.dist, self.basis, self.rank, self.eval_c(), self.basis.dealias)
 
 
-def _ex(dist):
-    return dist.executor
-
-
 def _backward(dist, basis, rank, c, scales, upto=None):
     """upto "azimuth" (reduced analysis tasks): stop at the coordinate components [nc][2 nm][Nt] in front of the FFT"""
-    ex = _ex(dist)
+    ex = dist.executor
     nc = 2 ** rank
     Np, Nt = basis.grid_shape(scales)
     t1 = ex.empty((nc, 2 * basis.nm, Nt))
@@ -565,7 +523,7 @@ def _backward(dist, basis, rank, c, scales, upto=None):
 
 
 def _forward(dist, basis, rank, g, scales, upto=None):
-    ex = _ex(dist)
+    ex = dist.executor
     nc = 2 ** rank
     Np, Nt = basis.grid_shape(scales)
     t1 = ex.empty((nc, 2 * basis.nm, Nt))
@@ -691,10 +649,11 @@ class SField(HostMirror, SOperand):
             cache[id(self)] = g
         return g
 
-    def lin(self, variables, basis):
+    def lin(self, variables):
         """{variable index: TermList acting on that variable's coefficients}; raises if not a problem variable."""
         for i, v in enumerate(variables):
             if v is self:
+                basis = _basis_of(*variables)           # the problem's basis: a constant variable has none of its own
                 if self.basis is None:
                     return {i: op_termlist("convert_constant", basis, 0)}, False
                 return {i: TermList.identity(self.ncomp, basis.nm, basis.nl)}, False
@@ -714,48 +673,20 @@ def _basis_of(*ops):
     return None
 
 
-class SScale(SOperand):
-    def __init__(self, a, arg):
-        self.a, self.arg, self.args = float(a), arg, (arg,)
-        self.dist, self.basis, self.rank = arg.dist, arg.basis, arg.rank
-
-    def eval_c(self):
-        ex = _ex(self.dist)
-        c = self.arg.eval_c()
-        out = ex.empty(tuple(c.shape))
-        ex.lincomb(out, [c], [self.a])
-        return out
-
+class SScale(Scale, SOperand):
     def eval_g(self):
-        ex = _ex(self.dist)
+        ex = self.dist.executor
         g = self.arg.eval_g()
         out = ex.empty(tuple(g.shape))
         ex.lincomb(out, [g], [self.a])
         return out
 
-    def lin(self, variables, basis):
-        d, dt = self.arg.lin(variables, basis)
-        return {i: tl.scaled(self.a) for i, tl in d.items()}, dt
 
-
-class SAdd(SOperand):
-    @staticmethod
-    def make(a, b):
-        if isinstance(b, numbers.Number):
-            if b == 0:
-                return a
-            raise NotImplementedError("adding a number to a sphere field")
-        if isinstance(a, numbers.Number):
-            if a == 0:
-                return b
-            raise NotImplementedError("adding a number to a sphere field")
-        return SAdd(a, b)
+class SAdd(Add, SOperand):
+    geometry = "sphere"
 
     def __init__(self, a, b):
-        if a.rank != b.rank:
-            raise ValueError("cannot add tensors of different rank")
-        self.args = (a, b)
-        self.dist, self.rank = a.dist, a.rank
+        Add.__init__(self, a, b)
         self.basis = _basis_of(a, b)
 
     def _coef_of(self, a):
@@ -765,11 +696,11 @@ class SAdd(SOperand):
             f._sync_to_device()
             nat = np.zeros((1, 2 * self.basis.nm, self.basis.nl))
             nat[0, 0, 0] = float(f._const) / SphereBasis.constant_mode_value
-            return _ex(self.dist).from_host(nat)
+            return self.dist.executor.from_host(nat)
         return a.eval_c()
 
     def eval_c(self):
-        ex = _ex(self.dist)
+        ex = self.dist.executor
         cs = [self._coef_of(a) for a in self.args]
         out = ex.empty(tuple(cs[0].shape))
         ex.lincomb(out, cs, [1.0, 1.0])
@@ -778,23 +709,11 @@ class SAdd(SOperand):
     def eval_g(self):
         if any(a.basis is None for a in self.args):
             return SOperand.eval_g(self)
-        ex = _ex(self.dist)
+        ex = self.dist.executor
         gs = [a.eval_g() for a in self.args]
         out = ex.empty(tuple(gs[0].shape))
         ex.lincomb(out, gs, [1.0, 1.0])
         return out
-
-    def lin(self, variables, basis):
-        out, anydt = {}, None
-        for a in self.args:
-            d, dt = a.lin(variables, basis)
-            if anydt is None:
-                anydt = dt
-            elif anydt != dt:
-                raise NonlinearError("cannot mix dt and non-dt terms inside one sum node; write them as separate terms")
-            for i, tl in d.items():
-                out[i] = out[i] + tl if i in out else tl
-        return out, bool(anydt)
 
 
 class SLinear(SOperand):
@@ -813,11 +732,11 @@ class SLinear(SOperand):
             raise ValueError("div needs a tensor of rank >= 1")
         self._dev = None
 
-    def termlist(self, basis=None):
-        return op_termlist(self.kind, basis or self.basis, self.arg.rank)
+    def termlist(self):
+        return op_termlist(self.kind, self.basis, self.arg.rank)
 
     def eval_c(self):
-        ex = _ex(self.dist)
+        ex = self.dist.executor
         if self._dev is None or self._dev[0] is not ex:
             tl = self.termlist()
             self._dev = (ex, ex.make_sphere_terms(self.basis.nm, self.basis.nl, tl.ncomp_out, tl.terms))
@@ -826,9 +745,9 @@ class SLinear(SOperand):
         self._dev[1].apply(x, y)
         return y
 
-    def lin(self, variables, basis):
-        d, dt = self.arg.lin(variables, basis)
-        tl = self.termlist(basis)
+    def lin(self, variables):
+        d, dt = self.arg.lin(variables)
+        tl = self.termlist()
         return {i: tl.compose(t) for i, t in d.items()}, dt
 
 
@@ -841,44 +760,8 @@ class SAverage(SLinear):
         self.is_constant = True
 
 
-class SDt(SOperand):
-    def __init__(self, arg):
-        self.arg, self.args = arg, (arg,)
-        self.dist, self.basis, self.rank = arg.dist, arg.basis, arg.rank
-
-    def has_dt(self):
-        return True
-
-    def lin(self, variables, basis):
-        d, dt = self.arg.lin(variables, basis)
-        if dt:
-            raise NonlinearError("nested time derivatives")
-        return d, True
-
-    def eval_c(self):
-        raise ValueError("dt() cannot be evaluated")
-
-
-def _bilinear_terms(rank_a, rank_b, contract):
-    """(ic, ia, ib, coef) of the grid-space product of coordinate components: outer product (contract False) or
-    contraction of the last index of a with the first of b (DotProduct, core/arithmetic.py:246-251, 855-866)."""
-    ia_list = list(np.ndindex(*((2,) * rank_a)))
-    ib_list = list(np.ndindex(*((2,) * rank_b)))
-    if contract:
-        out_list = list(np.ndindex(*((2,) * (rank_a + rank_b - 2))))
-    else:
-        out_list = list(np.ndindex(*((2,) * (rank_a + rank_b))))
-    terms = []
-    for ia, ta in enumerate(ia_list):
-        for ib, tb in enumerate(ib_list):
-            if contract:
-                if ta[-1] != tb[0]:
-                    continue
-                tc = tuple(ta[:-1]) + tuple(tb[1:])
-            else:
-                tc = tuple(ta) + tuple(tb)
-            terms.append((out_list.index(tc), ia, ib, 1.0))
-    return terms, len(out_list)
+class SDt(Dt, SOperand):
+    pass
 
 
 class SProduct(SOperand):
@@ -899,21 +782,24 @@ class SProduct(SOperand):
             self.rank = a.rank + b.rank
 
     def eval_g(self):
-        ex = _ex(self.dist)
+        ex = self.dist.executor
         a, b = self.args
         ga, gb = a.eval_g(), b.eval_g()
-        terms, nout = _bilinear_terms(a.rank, b.rank, self.contract)
+        terms, nout = bilinear_terms(2, a.rank, b.rank, self.contract)
         Np, Nt = self.basis.grid_shape(self.basis.dealias)
         out = ex.empty((nout, Np, Nt))
         ex.bilinear(out, nout, ga, gb, Np * Nt, terms)
         return out
 
-    def lin(self, variables, basis):
+    def lin(self, variables):
         raise NonlinearError("products of fields are nonlinear")
 
 
 class SDot(SProduct):
     contract = True
+
+
+SOperand.scale_type, SOperand.add_type, SOperand.product, SOperand.dot = SScale, SAdd, SProduct, SDot
 
 
 # ---- reduced analysis tasks (core/sphreduce.py) ----------------------------------------------------------------------
@@ -948,9 +834,6 @@ class SReduced(sphreduce.ReducedResult, SOperand):
     def _tensor_shape(self):
         return (2,) * self.rank
 
-    def lin(self, variables, basis):
-        raise NonlinearError("%s in an equation" % self.what)
-
 
 class SAzimuthalInterp(SReduced):
     """f(phi=phi0) (InterpolateAzimuth, core/basis.py:5578-5634) -> (..., 1, Ntheta_g)"""
@@ -963,7 +846,7 @@ class SAzimuthalInterp(SReduced):
         SReduced.__init__(self, arg, position=float(position))
 
     def _device(self, scales):
-        ex, basis, nc = _ex(self.dist), self.basis, self.ncomp
+        ex, basis, nc = self.dist.executor, self.basis, self.ncomp
         Np, Nt = basis.grid_shape(scales)
         if self._grid is not None and scales == tuple(basis.dealias):
             t = _forward(self.dist, basis, self.rank, self._grid, scales, upto="azimuth")
@@ -984,7 +867,7 @@ class SColatitudeInterp(SReduced):
         SReduced.__init__(self, arg, position=float(position))
 
     def _device(self, scales):
-        ex, basis, rank, nc = _ex(self.dist), self.basis, self.rank, self.ncomp
+        ex, basis, rank, nc = self.dist.executor, self.basis, self.rank, self.ncomp
         Np, Nt = basis.grid_shape(scales)
         c = self._coeff_field().require_coeff_space()
         t1 = sphreduce.contract_rows(ex, basis._plans, ("theta", rank, self.position), c, nc * 2 * basis.nm, basis.nl, 1,
@@ -1011,7 +894,7 @@ class SAzimuthalAverage(SReduced):
         SReduced.__init__(self, arg)
 
     def _device(self, scales):
-        ex, basis, rank, nc = _ex(self.dist), self.basis, self.rank, self.ncomp
+        ex, basis, rank, nc = self.dist.executor, self.basis, self.rank, self.ncomp
         Np, Nt = basis.grid_shape(scales)
         nl = basis.nl
         one = np.ones((1, 1))
@@ -1069,7 +952,7 @@ def ave(a, *coords):
     if len(coords) == 1 and isinstance(coords[0], (tuple, list)):
         coords = tuple(coords[0])
     if isinstance(a, SReduced):
-        raise NotImplementedError("average of a reduced operand (%s): reductions of reductions are not supported" % a.what)
+        raise sphreduce.reduction_refused("average", a.what)
     if len(coords) == 1 and isinstance(a, SOperand):
         az = a.dist.coordsys.azimuth
         if coords[0] is az or coords[0] == az.name:
@@ -1086,16 +969,13 @@ def dt(a):
 # ==================================================================================================
 
 class SphereProblem(CurvilinearProblem):
-    operand_type, add_type, scale_type = SOperand, SAdd, SScale
+    operand_type = SOperand
     operators = dict(grad=grad, div=div, lap=lap, skew=skew, MulCosine=MulCosine, ave=ave, dt=dt,
                      Gradient=grad, Divergence=div, Laplacian=lap, Skew=skew, Average=ave, TimeDerivative=dt)
 
     def __init__(self, variables, namespace=None, time="t"):
         super().__init__(variables, namespace, time)
         self.basis = _basis_of(*self.variables)
-
-    def _lin(self, node):
-        return node.lin(self.variables, self.basis)
 
     def _numeric_rhs(self, rhs):
         if rhs != 0:                    # (deliberate: the shell keeps such a number)
@@ -1116,21 +996,6 @@ class SphereLBVP(SphereProblem):
     @property
     def solver_class(self):
         return SphereBoundaryValueSolver
-
-
-class _SpherePack:
-    """matvec interface the shared timesteppers use (pack.matvec(id, x, y))."""
-
-    def __init__(self, solver):
-        self.solver = solver
-        self.mats = []
-
-    def add(self, dev_terms):
-        self.mats.append(dev_terms)
-        return len(self.mats) - 1
-
-    def matvec(self, mid, x, y):
-        self.mats[mid].apply(x, y)
 
 
 class SphereSolverBase:
@@ -1170,7 +1035,7 @@ class SphereSolverBase:
         # system term lists
         self.M_tl = self._system_termlist("M")
         self.L_tl = self._system_termlist("L")
-        self.pack = _SpherePack(self)
+        self.pack = MatvecPack()
         self.M_id = self.pack.add(self.ex.make_sphere_terms(nm, nl, self.R, self.M_tl.terms))
         self.L_id = self.pack.add(self.ex.make_sphere_terms(nm, nl, self.R, self.L_tl.terms))
         # state vector; variable coefficient arrays are views into it

@@ -22,6 +22,7 @@ import numbers
 import numpy as np
 
 from ..tools import sphere as sph
+from .curvioperand import NonlinearError
 
 
 def azimuth_weights(nm, phi0):
@@ -85,6 +86,11 @@ def contract_rows(ex, store, key, x, outer, n, inner, make_rows):
     return ex.axis_contract_rows(x, outer, n, inner, *dev)
 
 
+def reduction_refused(what, inner):
+    """the error of a reduction (`what`) of an operand that is a reduced task already (`inner`: its name)"""
+    return NotImplementedError("%s of a reduced operand (%s): reductions of reductions are not supported" % (what, inner))
+
+
 class ReducedResult:
     """What the reduced tasks of both systems share: an ANALYSIS-ONLY operand whose grid data keep the reduced axes with
     size one (constant axes of an output file).  Subclasses set `what`, `const_axes`, and give `_device(scales)` -> device
@@ -95,9 +101,8 @@ class ReducedResult:
     dim = 3
 
     def _init(self, arg, **params):
-        if isinstance(arg, ReducedResult) or getattr(arg, "is_reduction", False):
-            raise NotImplementedError("%s of a reduced operand (%s): reductions of reductions are not supported"
-                                      % (self.what, getattr(arg, "what", "interpolation")))
+        if isinstance(arg, ReducedResult):
+            raise reduction_refused(self.what, arg.what)
         self.args, self.params = (arg,), params
         self.dist, self.basis, self.rank = arg.dist, arg.basis, arg.rank
         self.scales = (1.0,) * self.dim
@@ -106,8 +111,7 @@ class ReducedResult:
         self._host = {}
 
     def __call__(self, **kw):
-        raise NotImplementedError("interpolation of a reduced operand (%s): reductions of reductions are not supported"
-                                  % self.what)
+        raise reduction_refused("interpolation", self.what)
 
     def _remedy(self, scales):
         if scales is None:
@@ -172,3 +176,6 @@ class ReducedResult:
 
     def has_dt(self):
         return False
+
+    def lin(self, variables):
+        raise NonlinearError("%s in an equation" % self.what)
