@@ -823,6 +823,24 @@ class ShOperand(CurviOperand):
             return ShUnsupported("interpolation along %r" % name, self)
         return ShLinear("interp", self, position=float(pos))
 
+    def cfl_term(self, velocity):
+        """(term, own grid shape, function giving the device grid data) of this operand in the fused CFL reduction
+        (HipExecutor.cfl_sum_max): a vector on a shell basis as a velocity (Spherical3DAdvectiveCFL, core/basis.py:
+        6183-6204), a scalar as a frequency, both at the dealias scales."""
+        shell = self.basis
+        if not isinstance(shell, ShellBasis):
+            raise NotImplementedError("CFL frequencies of operands without a shell basis")
+        if velocity:
+            if tuple(self.sig) != (3,):
+                raise ValueError("CFL velocity must be a vector field on a shell")
+            term = dict(kind="shell", inv=_cfl_spacings(shell, self.dist.executor))
+        else:
+            if self.rank != 0:
+                raise ValueError("Frequency must be a scalar")
+            term = dict(kind="scalar")
+        Np, Nt, Ng = shell.grid_shape(shell.dealias)
+        return term, (int(Np), int(self.dist.theta_range(Nt)[1]), int(Ng)), self.eval_g
+
     def grid_native(self):
         """Grid data when the operand is formed in grid space (products), else None."""
         return None
@@ -1804,6 +1822,13 @@ class ConstField(ShOperand):
     def eval_c(self):
         raise NotImplementedError("constants are converted to a shell basis before evaluation")
 
+    def cfl_term(self, velocity):
+        """A constant as a CFL frequency (ShOperand.cfl_term): one point along every axis"""
+        if velocity:
+            raise ValueError("CFL velocity must be a vector field on a shell")
+        ex = self.dist.executor
+        return dict(kind="scalar"), (1, 1, 1), lambda: ex.from_host(np.array(self.value, dtype=np.float64).reshape(1, 1, 1, 1))
+
     # solver interface
     def _cshape_in(self, shell):
         sb = shell.sphere
@@ -1834,22 +1859,45 @@ class RadialField(ShOperand):
     def lin(self, variables):
         raise NonlinearError("a radial field is a coefficient, not a variable")
 
+    def grid_profile(self, Ng):
+        """[3^rank][Ng]: the radial profile re-sampled spectrally on the radial Gauss grid of Ng points"""
+        from ..tools import jacobi
+        shell = self.shell_basis
+        nc = 3 ** self.rank
+        z, w = jacobi.quadrature(shell.Nr, shell.alpha[0], shell.alpha[1])
+        P = np.asarray(jacobi.polynomials(shell.Nr, shell.alpha[0], shell.alpha[1], z))
+        coef = self._g.reshape(nc, shell.Nr) @ (P * np.asarray(w, dtype=np.float64)).T
+        zg, _ = jacobi.quadrature(Ng, shell.alpha[0], shell.alpha[1])
+        Pg = np.asarray(jacobi.polynomials(shell.Nr, shell.alpha[0], shell.alpha[1], zg), dtype=np.float64)
+        return coef @ Pg
+
+    def cfl_term(self, velocity):
+        """A radial profile as a CFL frequency (ShOperand.cfl_term): [1][1][1][Nr_g] on the device, one point along both
+        angles -- the fused reduction reads it with stride 0 there."""
+        if velocity or self.rank != 0:
+            raise ValueError("a radial field enters the CFL sum as a scalar frequency only")
+        shell = self.shell_basis
+        Ng = int(shell.grid_shape(shell.dealias)[2])
+        ex = self.dist.executor
+        store = getattr(shell, "_root", shell)._plans
+        key = ("cfl_profile", id(ex), id(self))
+
+        def data():
+            if key not in store or store[key][0] != self._g.tobytes():
+                store[key] = (self._g.tobytes(), ex.from_host(np.ascontiguousarray(self.grid_profile(Ng).reshape(1, 1, 1, Ng))))
+            return store[key][1]
+        return dict(kind="scalar"), (1, 1, Ng), data
+
     def grid_broadcast(self, ex, basis, shape):
         """coordinate components on the dealiased grid [3^rank][Nphi_g][Ntheta_local][Nr_g] (analysis products such as
         er @ flux): the radial profile is re-sampled spectrally on the finer radial grid and repeated over the angles"""
-        from ..tools import jacobi
         shell = self.shell_basis
         Np, Nt, Ng = shape
         key = ("ncc_grid", id(ex), id(self), shape)
         store = getattr(shell, "_root", shell)._plans
         if key not in store or store[key][0] != self._g.tobytes():
             nc = 3 ** self.rank
-            z, w = jacobi.quadrature(shell.Nr, shell.alpha[0], shell.alpha[1])
-            P = np.asarray(jacobi.polynomials(shell.Nr, shell.alpha[0], shell.alpha[1], z))
-            coef = self._g.reshape(nc, shell.Nr) @ (P * np.asarray(w, dtype=np.float64)).T
-            zg, _ = jacobi.quadrature(Ng, shell.alpha[0], shell.alpha[1])
-            Pg = np.asarray(jacobi.polynomials(shell.Nr, shell.alpha[0], shell.alpha[1], zg), dtype=np.float64)
-            prof = coef @ Pg                                   # [nc][Ng]
+            prof = self.grid_profile(Ng)                       # [nc][Ng]
             full = np.ascontiguousarray(np.broadcast_to(prof[:, None, None, :], (nc, Np, Nt, Ng)))
             store[key] = (self._g.tobytes(), ex.from_host(full))
         return store[key][1]
@@ -2022,19 +2070,24 @@ class ShellField(HostMirror, ShOperand):
         if self.rank != 1 or not isinstance(self.basis, ShellBasis):
             raise ValueError("CFL velocity must be a vector field on a shell")
         ex = self.ex
-        key = ("cfl", id(ex))
-        shell = self.basis
-        store = getattr(shell, "_root", shell)._plans
-        if key not in store:
-            sc = shell.dealias
-            r = shell.radius_grid(sc[2])
-            Lmax = shell.sphere.Lmax
-            h = r / np.sqrt(Lmax * (Lmax + 1)) if Lmax > 0 else np.full_like(r, np.inf)
-            dr = np.gradient(r, edge_order=2) * sc[2]
-            store[key] = (ex.from_host(np.ascontiguousarray(1.0 / h)), ex.from_host(np.ascontiguousarray(1.0 / np.abs(dr))))
-        inv_h, inv_dr = store[key]
+        inv_h, inv_dr = _cfl_spacings(self.basis, ex)
         g = self.eval_g()
         return ex.cfl_max_spherical(g, inv_h, inv_dr)
+
+
+def _cfl_spacings(shell, ex):
+    """device arrays (1 / horizontal spacing, 1 / radial spacing) over the dealiased radial grid (Spherical3DAdvectiveCFL.
+    cfl_spacing, core/basis.py:6187-6198)"""
+    key = ("cfl", id(ex))
+    store = getattr(shell, "_root", shell)._plans
+    if key not in store:
+        sc = shell.dealias
+        r = shell.radius_grid(sc[2])
+        Lmax = shell.sphere.Lmax
+        h = r / np.sqrt(Lmax * (Lmax + 1)) if Lmax > 0 else np.full_like(r, np.inf)
+        dr = np.gradient(r, edge_order=2) * sc[2]
+        store[key] = (ex.from_host(np.ascontiguousarray(1.0 / h)), ex.from_host(np.ascontiguousarray(1.0 / np.abs(dr))))
+    return store[key]
 
 
 # ==================================================================================================

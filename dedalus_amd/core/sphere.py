@@ -491,6 +491,26 @@ class SOperand(CurviOperand):
     def _result_field(self):
         return SField(self.dist, basis=self.basis, rank=self.rank)
 
+    def cfl_term(self, velocity):
+        """(term, own grid shape, function giving the device grid data) of this operand in the fused CFL reduction
+        (HipExecutor.cfl_sum_max), at the dealias scales: a vector as a velocity with the one spacing R / sqrt(Lmax
+        (Lmax + 1)) of S2AdvectiveCFL (core/basis.py:6156-6180; Lmax = 0: infinite), a scalar as a frequency."""
+        if velocity:
+            if self.rank != 1 or self.basis is None:
+                raise ValueError("CFL velocity must be a vector field on the sphere")
+            Lmax = self.basis.Lmax
+            term = dict(kind="s2", inv_h=float(np.sqrt(Lmax * (Lmax + 1)) / self.basis.radius))
+        else:
+            if self.rank != 0:
+                raise ValueError("Frequency must be a scalar")
+            term = dict(kind="scalar")
+        if self.basis is None:
+            return term, (1, 1), self._cfl_constant
+        return term, tuple(int(n) for n in self.basis.grid_shape(self.basis.dealias)), self.eval_g
+
+    def _cfl_constant(self):
+        raise NotImplementedError("CFL frequency of a constant expression on the sphere")
+
     # evaluation to device arrays ------------------------------------------------------------------------------
     def eval_c(self):
         """Device coefficient array [ncomp][2 nm][nl] (a fresh array or a field's own, never to be modified)."""
@@ -648,6 +668,11 @@ class SField(HostMirror, SOperand):
         if cache is not None:
             cache[id(self)] = g
         return g
+
+    def _cfl_constant(self):
+        """a field without a basis as a CFL frequency: its grid-space value, one point along both axes"""
+        self._sync_to_device()
+        return self.ex.from_host(np.array(float(self._const)).reshape(1, 1, 1))
 
     def lin(self, variables):
         """{variable index: TermList acting on that variable's coefficients}; raises if not a problem variable."""

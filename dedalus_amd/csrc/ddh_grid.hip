@@ -2,6 +2,7 @@
 //  - ddh_lincomb:        RHS assembly  y = sum_t alpha_t x_t   (timesteppers.py:617-623, 156-166)
 //  - ddh_grid_bilinear:  out[c] = sum_t coef_t a[ia_t] b[ib_t] (arithmetic.py:666-674, 708-728, 855-866)
 //  - ddh_grid_cfl:       max_x sum_c |u_c| / dx_c              (operators.py:4342-4419, basis.py:6078-6113)
+//  - ddh_grid_cfl_sum:   max_x sum_t f_t, velocities and scalar frequencies    (extras/flow_tools.py:199-204)
 //  - ddh_a2a_pack/unpack: block re-ordering around the RCCL all-to-all (transposes.pyx:359-445)
 // All are one read of each input and one write of the output with 16-byte accesses.
 #include "ddh_common.h"
@@ -145,6 +146,70 @@ cfl_spherical_kernel(double *result, const double *__restrict__ u, long n_ang, i
         const int ir = (int)(i % nr);
         const double up = u[i], ut = u[n + i], ur = u[2 * n + i];
         m = nan_max(m, sqrt(up * up + ut * ut) * inv_h[ir] + fabs(ur) * inv_dr[ir]);
+    }
+    red[threadIdx.x] = m;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (threadIdx.x < s) red[threadIdx.x] = nan_max(red[threadIdx.x], red[threadIdx.x + s]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) atomic_max_double(result, red[0]);
+}
+
+// Sum of CFL frequencies (CFL.compute_timestep, extras/flow_tools.py:199-204: sum(|f_j|) per grid point, then the
+// maximum): up to MAX_CFL_TERMS terms over ONE storage grid, one read of every operand, one launch.  The grid is
+// always three axes here (the host pads leading axes of length 1); an operand without a basis along an axis has
+// stride 0 there and is read from its own small array.
+constexpr int MAX_CFL_TERMS = 8;
+struct CflTerm {
+    const double *data;            // [ncomp][own grid]
+    const double *inv[MAX_AXES];   // velocity: 1/spacing per component; shell: inv_h, inv_dr over the last axis
+    long stride[MAX_AXES];         // of the operand's own grid, 0 along a broadcast axis
+    long cstride;                  // between components: the operand's own point count
+    double inv_h;                  // S2: sqrt(Lmax (Lmax + 1)) / R
+    int kind, ncomp;
+    int comp_axis[MAX_AXES];       // velocity: storage axis of each component, < 0: no basis there, no frequency
+};
+struct CflSumArgs {
+    CflTerm t[MAX_CFL_TERMS];
+    long len[MAX_AXES];
+    int nterms;
+};
+
+// I: the type of the index decomposition (unsigned while n < 2^32: a 64-bit division is several times the instructions)
+template <typename I>
+__global__ void __launch_bounds__(256) cfl_sum_kernel(double *result, long n, CflSumArgs a) {
+    __shared__ double red[256];
+    double m = 0.0;
+    const long stride = (long)gridDim.x * blockDim.x;
+    const I l1 = (I)a.len[1], l2 = (I)a.len[2];
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        // decompose i into axis indices (last axis fastest), once for all terms
+        const I q = (I)i / l2;
+        const long i2 = (long)((I)i - q * l2), i0 = (long)(q / l1), i1 = (long)(q - (q / l1) * l1);
+        double f = 0.0;
+        for (int t = 0; t < a.nterms; ++t) {
+            const CflTerm &T = a.t[t];
+            const double *u = T.data + (i0 * T.stride[0] + i1 * T.stride[1] + i2 * T.stride[2]);
+            double ft = 0.0;
+            if (T.kind == DDH_CFL_SCALAR) {
+                ft = fabs(u[0]);
+            } else if (T.kind == DDH_CFL_VELOCITY) {          // the arithmetic and order of cfl_kernel
+                for (int c = 0; c < T.ncomp; ++c) {
+                    const int ax = T.comp_axis[c];
+                    if (ax < 0) continue;
+                    ft += fabs(u[c * T.cstride]) * T.inv[c][ax == 0 ? i0 : (ax == 1 ? i1 : i2)];
+                }
+            } else if (T.kind == DDH_CFL_SHELL) {             // that of cfl_spherical_kernel
+                const double up = u[0], ut = u[T.cstride], ur = u[2 * T.cstride];
+                ft = sqrt(up * up + ut * ut) * T.inv[0][i2] + fabs(ur) * T.inv[1][i2];
+            } else {                                          // S2AdvectiveCFL, core/basis.py:6156-6180
+                const double up = u[0], ut = u[T.cstride];
+                ft = sqrt(up * up + ut * ut) * T.inv_h;
+            }
+            f += ft;
+        }
+        m = nan_max(m, f);
     }
     red[threadIdx.x] = m;
     __syncthreads();
@@ -460,6 +525,68 @@ int ddh_grid_cfl_spherical(double *result_d, const double *u, long n_ang, int nr
     DDH_HIP(hipMemsetAsync(result_d, 0, sizeof(double), as_stream(stream)));
     hipLaunchKernelGGL(cfl_spherical_kernel, dim3(stream_grid(n_ang * nr)), dim3(256), 0, as_stream(stream), result_d, u,
                        n_ang, nr, inv_h_d, inv_dr_d);
+    DDH_HIP(hipGetLastError());
+    return 0;
+}
+
+int ddh_grid_cfl_sum(double *result_d, int nterms, const ddh_cfl_term *terms_h, long n, const long *axis_len_h,
+                     int naxes, void *stream) {
+    if (nterms < 1 || nterms > MAX_CFL_TERMS) return fail("ddh_grid_cfl_sum: 1..8 terms supported");
+    if (naxes < 1 || naxes > MAX_AXES) return fail("ddh_grid_cfl_sum: 1..3 axes");
+    if (!result_d || !terms_h || !axis_len_h) return fail("ddh_grid_cfl_sum: null pointer");
+    CflSumArgs a;
+    a.nterms = nterms;
+    const int pad = MAX_AXES - naxes;          // the kernel's grid: leading axes of length 1
+    long tot = 1;
+    for (int ax = 0; ax < MAX_AXES; ++ax) {
+        a.len[ax] = ax < pad ? 1 : axis_len_h[ax - pad];
+        if (a.len[ax] < 1) return fail("ddh_grid_cfl_sum: axis lengths >= 1");
+        tot *= a.len[ax];
+    }
+    if (tot != n) return fail("ddh_grid_cfl_sum: axis lengths do not multiply to n");
+    for (int t = 0; t < nterms; ++t) {
+        const ddh_cfl_term &s = terms_h[t];
+        CflTerm &d = a.t[t];
+        if (s.kind < DDH_CFL_VELOCITY || s.kind > DDH_CFL_S2) return fail("ddh_grid_cfl_sum: unknown term kind");
+        if (!s.data) return fail("ddh_grid_cfl_sum: null operand");
+        d.kind = s.kind;
+        d.data = s.data;
+        d.inv_h = s.inv_h;
+        d.ncomp = s.kind == DDH_CFL_SCALAR ? 1 : (s.kind == DDH_CFL_SHELL ? 3 : (s.kind == DDH_CFL_S2 ? 2 : s.ncomp));
+        if (d.ncomp < 1 || d.ncomp > MAX_AXES) return fail("ddh_grid_cfl_sum: 1..3 velocity components");
+        long own = 1;
+        bool everywhere = true;
+        for (int ax = MAX_AXES - 1; ax >= 0; --ax) {
+            const bool b = ax < pad || s.bcast[ax - pad] != 0;
+            d.stride[ax] = b ? 0 : own;
+            if (!b) own *= a.len[ax];
+            if (ax >= pad && !b) everywhere = false;
+        }
+        d.cstride = own;
+        if (s.kind != DDH_CFL_SCALAR && everywhere) return fail("ddh_grid_cfl_sum: velocity broadcast along every axis");
+        for (int c = 0; c < MAX_AXES; ++c) {
+            d.inv[c] = nullptr;
+            d.comp_axis[c] = -1;
+        }
+        if (s.kind == DDH_CFL_VELOCITY) {
+            for (int c = 0; c < d.ncomp; ++c) {
+                if (s.comp_axis[c] >= naxes) return fail("ddh_grid_cfl_sum: component axis out of range");
+                if (s.comp_axis[c] < 0) continue;
+                if (!s.inv[c]) return fail("ddh_grid_cfl_sum: null spacing array");
+                d.comp_axis[c] = s.comp_axis[c] + pad;
+                d.inv[c] = s.inv[c];
+            }
+        } else if (s.kind == DDH_CFL_SHELL) {
+            if (!s.inv[0] || !s.inv[1]) return fail("ddh_grid_cfl_sum: null spacing array");
+            d.inv[0] = s.inv[0];
+            d.inv[1] = s.inv[1];
+        }
+    }
+    DDH_HIP(hipMemsetAsync(result_d, 0, sizeof(double), as_stream(stream)));
+    if (n < (1L << 32))
+        hipLaunchKernelGGL(cfl_sum_kernel<unsigned>, dim3(stream_grid(n)), dim3(256), 0, as_stream(stream), result_d, n, a);
+    else
+        hipLaunchKernelGGL(cfl_sum_kernel<long>, dim3(stream_grid(n)), dim3(256), 0, as_stream(stream), result_d, n, a);
     DDH_HIP(hipGetLastError());
     return 0;
 }

@@ -367,6 +367,32 @@ class HipExecutor:
         libhip.call("ddh_grid_cfl", ptr(res), ptr(u), ncomp, n, arr, libhip.as_ip(ca), ln, len(shape), self.dev.stream)
         return float(res.cpu().item())
 
+    def cfl_sum_max(self, terms, shape):
+        """max over the storage grid `shape` of the sum of CFL frequencies, one launch (ddh_grid_cfl_sum).  terms: dicts
+        in summation order with kind ("velocity" | "scalar" | "shell" | "s2"), data (device array [ncomp][own grid]),
+        bcast (per storage axis: the operand has one point there); velocity: comp_axis (storage axis per component,
+        None = no basis along it) and inv (device 1/dx per component); shell: inv = (inv_h, inv_dr) over r; s2: inv_h."""
+        kinds = dict(velocity=libhip.CFL_VELOCITY, scalar=libhip.CFL_SCALAR, shell=libhip.CFL_SHELL, s2=libhip.CFL_S2)
+        arr = (libhip.CflTerm * max(len(terms), 1))()
+        for t, d in zip(arr, terms):
+            t.kind, t.data = kinds[d["kind"]], d["data"].data_ptr()
+            for ax, b in enumerate(d["bcast"]):
+                t.bcast[ax] = 1 if b else 0
+            if d["kind"] == "velocity":
+                t.ncomp = len(d["comp_axis"])
+                for c, (ax, inv) in enumerate(zip(d["comp_axis"], d["inv"])):
+                    t.comp_axis[c] = -1 if ax is None else int(ax)
+                    t.inv[c] = None if ax is None else inv.data_ptr()
+            elif d["kind"] == "shell":
+                t.inv[0], t.inv[1] = d["inv"][0].data_ptr(), d["inv"][1].data_ptr()
+            elif d["kind"] == "s2":
+                t.inv_h = float(d["inv_h"])
+        res = self.dev.zeros((1,))
+        ln = (C.c_long * len(shape))(*[int(x) for x in shape])
+        libhip.call("ddh_grid_cfl_sum", ptr(res), len(terms), arr, int(np.prod(shape, dtype=np.int64)), ln, len(shape),
+                    self.dev.stream)
+        return float(res.cpu().item())
+
     def cfl_max_spherical(self, u, inv_h, inv_dr):
         """u [3][Nphi][Ntheta][Nr] (device), inv_h / inv_dr device arrays over r -> max CFL frequency (float)."""
         nr = int(u.shape[-1])

@@ -34,6 +34,15 @@ class PolyMat(C.Structure):
                 ("dx_h", C.POINTER(C.c_byte)), ("dy_h", C.POINTER(C.c_byte))]
 
 
+class CflTerm(C.Structure):
+    """ddh_cfl_term of include/dedalus_hip.h"""
+    _fields_ = [("kind", C.c_int), ("ncomp", C.c_int), ("data", C.c_void_p), ("bcast", C.c_int * 3),
+                ("comp_axis", C.c_int * 3), ("inv", C.c_void_p * 3), ("inv_h", C.c_double)]
+
+
+CFL_VELOCITY, CFL_SCALAR, CFL_SHELL, CFL_S2 = 0, 1, 2, 3         # DDH_CFL_* of include/dedalus_hip.h
+CFL_MAX_TERMS = 8
+
 _vp, _h, _hp = C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)
 _dp, _ip, _l, _i, _d = C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_long, C.c_int, C.c_double
 
@@ -111,6 +120,7 @@ SIGNATURES = {
     "ddh_grid_bilinear": [_vp, _i, _vp, _vp, _l, _i, _ip, _ip, _ip, _dp, _vp],
     "ddh_grid_cfl": [_vp, _vp, _i, _l, C.POINTER(_vp), _ip, C.POINTER(_l), _i, _vp],
     "ddh_grid_cfl_spherical": [_vp, _vp, _l, _i, _vp, _vp, _vp],
+    "ddh_grid_cfl_sum": [_vp, _i, C.POINTER(CflTerm), _l, C.POINTER(_l), _i, _vp],
     "ddh_grid_reduce": [_vp, _vp, _l, _vp, _vp],
     "ddh_grid_map": [_vp, _vp, _l, _i, _d, _vp],
     "ddh_grid_broadcast": [_vp, _vp, _i, C.POINTER(_l), _ip, _vp],

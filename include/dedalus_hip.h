@@ -373,6 +373,39 @@ int ddh_grid_cfl(double *result_d, const double *u, int ncomp, long n,
 int ddh_grid_cfl_spherical(double *result_d, const double *u, long n_ang, int nr, const double *inv_h_d,
                            const double *inv_dr_d, void *stream);
 
+/* Several CFL frequencies in one reduction: max over the grid of sum_t f_t, the terms added in list order (CFL.
+ * compute_timestep, extras/flow_tools.py:199-204: sum(np.abs(field['g'])) over the frequency fields in insertion order,
+ * then the maximum; add_velocity only adds AdvectiveCFL(velocity) as one more frequency, :220-233).  All terms share one
+ * storage grid axis_len_h[naxes] (1..3 axes, last fastest).  An operand without a basis along a storage axis sets
+ * bcast there: it holds one point along that axis and is read with stride 0 (NumPy broadcasting of the reference's sum),
+ * so a profile N(z) or a constant is read from its own small array.  Kinds:
+ *   DDH_CFL_VELOCITY  sum_c |u_c| * inv[c][index along comp_axis[c]], the arithmetic and order of the single-velocity
+ *                     entry point above (AdvectiveCFL core/operators.py:4342-4419, spacings core/basis.py:6078-6113);
+ *                     comp_axis[c] < 0: no basis along that component's axis, infinite spacing, the component adds
+ *                     nothing (basis.py:6103-6104) and is not read
+ *   DDH_CFL_SCALAR    |f|
+ *   DDH_CFL_SHELL     sqrt(u_phi^2 + u_theta^2) * inv[0][r] + |u_r| * inv[1][r], inv over the LAST storage axis
+ *                     (Spherical3DAdvectiveCFL core/basis.py:6183-6204)
+ *   DDH_CFL_S2        sqrt(u_phi^2 + u_theta^2) * inv_h, inv_h = sqrt(Lmax (Lmax + 1)) / R (S2AdvectiveCFL
+ *                     core/basis.py:6156-6180)
+ * Every term is non-negative or NaN; a NaN at any point of any term makes the result NaN, an all-zero grid gives 0.0.
+ * Errors, before anything is launched: not 1..DDH_CFL_MAX_TERMS terms, axis lengths that do not multiply to n, a
+ * velocity (any of the three kinds) broadcast along every axis, null pointers, a component axis out of range.
+ * Asynchronous on `stream`, no host synchronisation; the terms are copied into the kernel arguments.               */
+#define DDH_CFL_MAX_TERMS 8
+enum { DDH_CFL_VELOCITY = 0, DDH_CFL_SCALAR = 1, DDH_CFL_SHELL = 2, DDH_CFL_S2 = 3 };
+typedef struct {
+    int kind;
+    int ncomp;              /* DDH_CFL_VELOCITY: 1..3; fixed by the other kinds (1, 3, 2) */
+    const double *data;     /* device, [ncomp][the operand's own grid] */
+    int bcast[3];           /* per storage axis: nonzero = one point along it */
+    int comp_axis[3];       /* DDH_CFL_VELOCITY */
+    const double *inv[3];   /* device; DDH_CFL_VELOCITY: per component, DDH_CFL_SHELL: inv_h, inv_dr */
+    double inv_h;           /* DDH_CFL_S2 */
+} ddh_cfl_term;
+int ddh_grid_cfl_sum(double *result_d, int nterms, const ddh_cfl_term *terms_h, long n, const long *axis_len_h,
+                     int naxes, void *stream);
+
 /* out3_d = {min, max, sum} over n grid values (device), the local reductions of GlobalArrayReducer / GlobalFlowProperty
  * (extras/flow_tools.py:9-47, 49-111: np.min / np.max / np.sum of the grid data followed by an 8-byte Allreduce).
  * work_d: 3 * 1024 doubles of scratch.  Fixed reduction tree: the sum is reproducible from run to run.           */
