@@ -433,7 +433,7 @@ class HipBandMatsolver:
             for p in parts:
                 d_b = self.dev.from_host(np.ascontiguousarray(p).reshape(self.N, 1, 1))
                 d_x = self.dev.empty((self.N, 1, 1))
-                self.pack.solve(self.lu, d_b, d_x)
+                self.pack.solve(self.lu, [d_b], [1.0], d_x)
                 self.dev.sync()
                 sols.append(self.dev.to_host(d_x).reshape(self.N))
             if self.cx:

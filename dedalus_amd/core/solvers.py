@@ -1004,7 +1004,7 @@ class SolverBase:
 
     def rhs_tiling(self, lus):
         """Row length ny when the solver-internal right-hand-side vectors (the timestepper's M.X and F buffers) can use
-        the TILE-MAJOR layout [kx/8][ky/8][kx%8][ky%8] the sweeps read contiguously (ddh_pencil_solve_recombined_tiled,
+        the TILE-MAJOR layout [kx/8][ky/8][kx%8][ky%8] the sweeps read contiguously (ddh_pencil_solve_req::terms_tiled,
         include/dedalus_hip.h), else 0.  Needs: two Fourier axes with sizes that are multiples of 8, right-hand sides
         written by the forward transforms themselves (direct F) through the strided-axis wave kernel, the window-form M.X
         product -- properties of the problem, decided once -- and the lean forward sweep over real factors for EVERY
@@ -1053,17 +1053,28 @@ class SolverBase:
         if getattr(self, "modal", None) is not None:
             a, b = self._modal_lus[lu]
             self.modal.solve(a, b, [rhs], [1.0], out)
-        elif self.P_id is None:
-            self.pack.solve(lu, rhs, out)
-        elif hasattr(self.pack, "solve_recombined"):
-            Y = self.ex.empty((self.R, self.nx, self.ny))
-            self.pack.solve_recombined(lu, [rhs], [1.0], self.P_id, Y, out)
         else:
-            Y = self.ex.empty((self.R, self.nx, self.ny))
-            self.pack.solve(lu, rhs, Y)
-            self.pack.matvec(self.P_id, Y, out)
+            self._pack_solve(lu, [rhs], [1.0], out)
         if getattr(self, "solve_probe", None) is not None:
+            # (this label is recorded as it always was, whatever the pack and with or without P: deliberately not the
+            #  one `_pack_solve` returns from `solve_path_label`)
             self._probe_record(lu, rhs, out, path="ddh_pencil_solve_recombined (one materialised right-hand side)")
+
+    def _pack_solve(self, lu, xs, alphas, out, zero_rows=None, skip_rows=None, tiled=False, mx_out=None):
+        """The one call of the pack behind `solve` and `solve_lincomb`; returns the label of the feature set it used."""
+        Y = out if self.P_id is None else self.ex.empty((self.R, self.nx, self.ny))
+        if not getattr(self.pack, "solves_requests", False):
+            # the oracle's pack keeps the reference's steps apart (oracle/np_executor.py): axpy chain, solve, P mat-vec
+            self.pack.solve_lincomb(lu, xs, alphas, Y)
+            if self.P_id is not None:
+                self.pack.matvec(self.P_id, Y, out)
+            return solve_path_label(False)
+        if self.P_id is None:
+            self.pack.solve(lu, xs, alphas, out)
+            return solve_path_label(False)
+        self.pack.solve(lu, xs, alphas, out, p_mat_id=self.P_id, work=Y, zero_rows=zero_rows, skip_rows=skip_rows, tiled=tiled,
+                        mx=None if mx_out is None else (self.M_id, mx_out))
+        return solve_path_label(True, zero_rows is not None or skip_rows is not None, tiled, mx_out is not None)
 
     def _probe_record(self, lu, rhs, out, path, skip_rows=None, terms=1, zero_rows=None):
         """Parity probe (tests, bench.py `parity`): the right-hand side and the solution of the solve that just ran, on the
@@ -1119,7 +1130,7 @@ class SolverBase:
     def mx_f_zero_rows(self):
         """Device form (byte mask, fraction set) of `zero_rows_host`, or None.  A Runge-Kutta right-hand side built from M.X
         and F vectors only (timesteppers.RungeKuttaIMEX) passes it to the solve, whose forward sweep then does not read
-        those rows (ddh_pencil_solve_recombined_sparse)."""
+        those rows (ddh_pencil_solve_req::zero_rows)."""
         if getattr(self, "_zrows", "unset") != "unset":
             return self._zrows
         self._zrows = None
@@ -1166,7 +1177,7 @@ class SolverBase:
     def prepare_mx_emission(self, lu):
         """Whether the sweeps of factorization `lu` can write M.X (PencilPack.emits_mx) and the analysis of M P allows it;
         hands the tables of `mx_band_tables` to the factorization when both hold."""
-        if not hasattr(self.pack, "emits_mx") or self.P_id is None or getattr(self, "modal", None) is not None:
+        if not getattr(self.pack, "supports_mx_emission", False) or self.P_id is None or getattr(self, "modal", None) is not None:
             return False
         if not self.pack.emits_mx(lu, self.P_id):
             return False
@@ -1203,9 +1214,9 @@ class SolverBase:
             self.ex.lincomb(rhs, xs, alphas)
             self._last_rhs = rhs
             return self.solve(lu, rhs, out)
-        if tiled and (self.P_id is None or not hasattr(self.pack, "solve_recombined") or len(xs) > self.pack.MAX_RHS_TERMS):
+        if tiled and (self.P_id is None or not getattr(self.pack, "solves_requests", False) or len(xs) > self.pack.MAX_RHS_TERMS):
             raise RuntimeError("tile-major right-hand sides need the fused recombined solve")
-        if len(xs) > self.pack.MAX_RHS_TERMS or not hasattr(self.pack, "solve_lincomb"):
+        if len(xs) > self.pack.MAX_RHS_TERMS:
             rhs = self.ex.empty((self.R, self.nx, self.ny))
             self.ex.lincomb(rhs, xs, alphas)
             self._last_rhs = rhs                       # (kept for the parity tests)
@@ -1220,30 +1231,7 @@ class SolverBase:
             if tiled:
                 rhs_rec = self.untile_rows(rhs_rec)          # (the record and the tests' re-solves use the natural layout)
             self._last_rhs = rhs_rec
-        path = "ddh_pencil_solve_lincomb"
-        if self.P_id is None:
-            self.pack.solve_lincomb(lu, xs, alphas, out)
-        elif hasattr(self.pack, "solve_recombined"):
-            Y = self.ex.empty((self.R, self.nx, self.ny))
-            if tiled:
-                if mx_out is not None:
-                    self.pack.solve_recombined(lu, xs, alphas, self.P_id, Y, out, zero_rows=zero_rows, skip_rows=skip_rows,
-                                               tiled=True, mx=(self.M_id, mx_out))
-                    path = "ddh_pencil_solve_recombined_tiled_mx"
-                else:
-                    self.pack.solve_recombined(lu, xs, alphas, self.P_id, Y, out, zero_rows=zero_rows, skip_rows=skip_rows,
-                                               tiled=True)
-                    path = "ddh_pencil_solve_recombined_tiled"
-            elif zero_rows is not None or skip_rows is not None:
-                self.pack.solve_recombined(lu, xs, alphas, self.P_id, Y, out, zero_rows=zero_rows, skip_rows=skip_rows)
-                path = "ddh_pencil_solve_recombined_sparse"
-            else:
-                self.pack.solve_recombined(lu, xs, alphas, self.P_id, Y, out)
-                path = "ddh_pencil_solve_recombined"
-        else:
-            Y = self.ex.empty((self.R, self.nx, self.ny))
-            self.pack.solve_lincomb(lu, xs, alphas, Y)
-            self.pack.matvec(self.P_id, Y, out)
+        path = self._pack_solve(lu, xs, alphas, out, zero_rows, skip_rows, tiled, mx_out)
         if probe is not None:
             skip_h = None
             if skip_rows is not None:
@@ -1495,6 +1483,19 @@ class SolverBase:
             logger.warning("explicit block inverses: ||B^T X - I|| = %.1e > %.0e, the sweeps stay" % (worst, tol))
             return False
         return True
+
+
+def solve_path_label(fused_p, masks=False, tiled=False, mx=False):
+    """The `path` of a parity-probe record: the name of the feature set a solve request used.  The strings were once the
+    names of one library entry point per feature set; they stay as they are, character for character, because the
+    BENCH_*.json history records them as `solve_paths` and tests/test_gpu_reference_pencils.py asserts on them.
+    fused_p: the pack applied P (p_mat_id of the request); masks: zero_rows or skip_rows given; tiled: tile-major terms;
+    mx: M.X written by the backward sweep."""
+    if not fused_p:
+        return "ddh_pencil_solve_lincomb"
+    if tiled:
+        return "ddh_pencil_solve_recombined_tiled_mx" if mx else "ddh_pencil_solve_recombined_tiled"
+    return "ddh_pencil_solve_recombined_sparse" if masks else "ddh_pencil_solve_recombined"
 
 
 def mx_band_tables(row, col, coef, row_perm, col_perm, n, nh, row_code, col_code, width):

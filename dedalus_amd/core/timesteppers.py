@@ -5,7 +5,7 @@ Same schemes, names and stage algebra as dedalus/core/timesteppers.py:
   multistep (:34-187)   (a0 M + b0 L) X_n = sum_j c_j F_{n-j} - sum_j a_j M X_{n-j} - sum_j b_j L X_{n-j}
   Runge-Kutta (:498-644) (M + k H_ii L) X_i = M X_0 + k sum_j A_ij F_j - k sum_j H_ij L X_j
 but every per-subproblem Python loop is one batched kernel over all pencils:
-  M.X / L.X  -> ddh_pencil_matvec,   RHS assembly -> ddh_lincomb,   LHS solve -> ddh_pencil_solve,
+  M.X / L.X  -> ddh_pencil_matvec,   RHS assembly + LHS solve -> one ddh_pencil_solve request (ddh_lincomb without it),
   LHS refactorisation (when a0,b0 or k*H_ii change) -> ddh_pencil_factor.
 
 The variable-step multistep coefficients are not tabulated: they are computed from their defining
@@ -85,14 +85,8 @@ class _SolveMixin:
     def _solve_combination(self, xs, al, lu, zero_rows=None, skip_rows=None, tiled=False, mx_out=None):
         s = self.solver
         if hasattr(s, "solve_lincomb"):
-            if mx_out is not None:
-                s.solve_lincomb(lu, xs, al, s.X, zero_rows=zero_rows, skip_rows=skip_rows, tiled=True, mx_out=mx_out)
-            elif tiled:
-                s.solve_lincomb(lu, xs, al, s.X, zero_rows=zero_rows, skip_rows=skip_rows, tiled=True)
-            elif zero_rows is not None or skip_rows is not None:
-                s.solve_lincomb(lu, xs, al, s.X, zero_rows=zero_rows, skip_rows=skip_rows)
-            else:
-                s.solve_lincomb(lu, xs, al, s.X)
+            s.solve_lincomb(lu, xs, al, s.X, zero_rows=zero_rows, skip_rows=skip_rows, tiled=tiled or mx_out is not None,
+                            mx_out=mx_out)
         else:
             s.ex.lincomb(self.RHS, xs, al)
             s.solve(lu, self.RHS, s.X)

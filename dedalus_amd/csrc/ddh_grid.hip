@@ -403,7 +403,7 @@ tile_rows_kernel(const double *__restrict__ src, double *__restrict__ dst, long 
 extern "C" {
 
 /* nrows rows of [nx][ny] doubles between the natural layout and the tile-major layout of the solver's system vectors
- * ([kx / 8][ky / 8][kx % 8][ky % 8] within a row; ddh_pencil_set_state_tiled, ddh_pencil_solve_recombined_tiled): to_tiled = 1
+ * ([kx / 8][ky / 8][kx % 8][ky % 8] within a row; ddh_pencil_set_state_tiled, ddh_pencil_solve_req::terms_tiled): to_tiled = 1
  * natural -> tiled, 0 tiled -> natural.  Out of place; nx and ny multiples of 8.  band_rows != 0: the tiled side is a block
  * of nrows rows of a kx-band-major vector of band_rows rows ([kx / 8][band_rows][ky / 8][8][8]; its pointer = that of the
  * block's first row in band 0), the natural side the nrows rows [nrows][nx][ny].  The host layer uses it where a state

@@ -106,7 +106,7 @@ struct LuDev {
     const int *rowperm, *colperm;  // logical -> physical
     const unsigned char *row_axes, *col_axes;   // per logical border row / col: validity bits
     const unsigned char *row_code, *col_code;   // real mode, per logical row / col: bit0 rotate by i, bit1 sign for -kx
-    // column recombination X = P Y fused into the backward sweep (ddh_pencil_solve_recombined): P in logical (graded)
+    // column recombination X = P Y fused into the backward sweep (ddh_pencil_solve_req::p_mat_id): P in logical (graded)
     // ordering is unit upper banded, pband[j * PBW + d - 1] = P[j, j + d], d = 1..PBW; null = not fused
     const double *pband;
     // Partner pencils (ddh_pencil_set_pairing): when the problem is symmetric under the exchange of the two Fourier axes,
@@ -140,7 +140,7 @@ struct LuDev {
 
 constexpr int PBW = 12;
 
-// M.X emitted by the backward sweep (ddh_pencil_solve_recombined_tiled_mx).  With the recombination fused the register
+// M.X emitted by the backward sweep (ddh_pencil_solve_req::m_mat_id).  With the recombination fused the register
 // window of solve_backward_kernel holds y_j .. y_(j + WT) of x = P y when step j ends; row i of the band of M P (graded,
 // logical ordering -- real, wavenumber-independent) whose columns lie in that window is formed there:
 //     band[j * MXW + d] = (M P)[row[j], j + d], d = 0 .. MXW - 1;   row[j] = the logical equation row emitted at step j, -1: none
@@ -570,7 +570,7 @@ band_matvec_kernel(PencilDev P, MatDev A, const double *__restrict__ x, double *
     const long plane = P.nx * P.ny;
     const long off0 = state_cell(P, 2 * c.mx, 2 * c.my), off1 = state_cell(P, 2 * c.mx + 1, 2 * c.my);
     const long xrs = state_row_stride(P);
-    // (y tile-major: ddh_pencil_matvec_update_tiled)
+    // (y tile-major: DDH_MATVEC_TILED)
     const long yoff0 = out_tiled ? tile_offset(2 * c.mx, 2 * c.my, P.ny) : (2 * c.mx) * P.ny + 2 * c.my;
     const long yoff1 = out_tiled ? tile_offset(2 * c.mx + 1, 2 * c.my, P.ny) : (2 * c.mx + 1) * P.ny + 2 * c.my;
     const int rr0 = blockIdx.y * rows_per_chunk;
@@ -618,7 +618,7 @@ band_matvec_kernel(PencilDev P, MatDev A, const double *__restrict__ x, double *
             v0 = make_double2(0.5 * (accP.x + accQ.x), 0.5 * (accP.y + accQ.y));
             v1 = make_double2(0.5 * (accP.y - accQ.y), 0.5 * (accQ.x - accP.x));
         }
-        if (base < 0 && keep_empty) continue;    // ddh_pencil_matvec_update: rows without terms are left as they are
+        if (base < 0 && keep_empty) continue;    // DDH_MATVEC_OWNED: rows without terms are left as they are
         double *yr = y + (long)r * plane;
         *reinterpret_cast<double2 *>(yr + yoff0) = v0;
         *reinterpret_cast<double2 *>(yr + yoff1) = v1;
@@ -745,7 +745,7 @@ struct RhsSrc {
     double a[RHS_MAX];
     const unsigned char *zrow;   // optional, per row of the system vectors: 1 = the row is zero in EVERY term (not read)
     const unsigned char *skip;   // optional, per row of the solution: 1 = the caller does not need the row (not written)
-    int tiled;                   // 1: the term vectors are stored tile-major (tile_offset), see ddh_pencil_solve_recombined_tiled
+    int tiled;                   // 1: the term vectors are stored tile-major (tile_offset), see ddh_pencil_solve_req::terms_tiled
 };
 
 template <int NF, int XD = 1>
@@ -2958,7 +2958,7 @@ static unsigned deep_block(long threads) {
     return threads / 128 >= 256 ? 128u : 64u;
 }
 
-// The kernels of one solve, decided once by sweep_plan: launch_solve executes the plan, solve_recombined_impl learns from
+// The kernels of one solve, decided once by sweep_plan: launch_solve executes the plan, ddh_pencil_solve learns from
 // it whether the recombination is fused, ddh_pencil_lu_info reports it.
 enum class FwdSweep {
     coop,         // solve_forward_coop_kernel: CH lanes per system
@@ -3457,8 +3457,8 @@ static int launch_matvec(PencilPack *pp, int mat_id, const double *x, double *y,
     if (P.nf == 2 && A.band && ps.nz == 0 && !A.order && (blocks >= 64 || out_tiled))
         hipLaunchKernelGGL(band_matvec_kernel, grid, dim3(256), 0, s, P, A, x, y, rpc, keep_empty, out_tiled);
     else if (out_tiled)
-        return fail("pencil_matvec_update_tiled: only the window-form mat-vec (real, wavenumber-independent bands; two Fourier "
-                    "axes) writes the tile-major layout");
+        return fail("pencil_matvec: DDH_MATVEC_TILED: only the window-form mat-vec (real, wavenumber-independent bands; two "
+                    "Fourier axes) writes the tile-major layout");
     else if (P.nf == 2)
         hipLaunchKernelGGL(matvec_kernel<2>, grid, dim3(256), 0, s, P, A, x, y, ps, rpc);
     else if (P.nf == 1)
@@ -3471,7 +3471,7 @@ static int launch_matvec(PencilPack *pp, int mat_id, const double *x, double *y,
 
 /* The state vector X -- the solution vector of every solve and the input vector of every mat-vec of this pack from now on --
  * is stored tile-major ([kx / 8][ky / 8][kx % 8][ky % 8] within a row, like the right-hand-side vectors of
- * ddh_pencil_solve_recombined_tiled): a wavefront's stores of a solution row are two 512-byte runs instead of sixteen 64-byte
+ * ddh_pencil_solve_req::terms_tiled): a wavefront's stores of a solution row are two 512-byte runs instead of sixteen 64-byte
  * runs.  Two Fourier axes with storage sizes that are multiples of 8; on = 0 returns to the natural layout. */
 int ddh_pencil_set_state_tiled(ddh_handle pack, int on) {
     PencilPack *pp = (PencilPack *)lookup_handle(pack, H_PENCIL);
@@ -3483,30 +3483,16 @@ int ddh_pencil_set_state_tiled(ddh_handle pack, int on) {
     return 0;
 }
 
-int ddh_pencil_matvec(ddh_handle pack, int mat_id, const double *x, double *y, void *stream) {
+int ddh_pencil_matvec(ddh_handle pack, int mat_id, const double *x, double *y, int flags, void *stream) {
     PencilPack *pp = (PencilPack *)lookup_handle(pack, H_PENCIL);
     if (!pp) return -1;
+    if (flags & ~(DDH_MATVEC_OWNED | DDH_MATVEC_TILED)) return fail("pencil_matvec: unknown flags");
+    const int tiled = (flags & DDH_MATVEC_TILED) != 0;
+    if (tiled && (pp->dev.nf != 2 || (pp->dev.nx & 7) || (pp->dev.ny & 7)))
+        return fail("pencil_matvec: DDH_MATVEC_TILED needs two Fourier axes with storage sizes that are multiples of 8");
     PostSolve ps;
     memset(&ps, 0, sizeof(ps));
-    return launch_matvec(pp, mat_id, x, y, ps, stream);
-}
-
-int ddh_pencil_matvec_update(ddh_handle pack, int mat_id, const double *x, double *y, void *stream) {
-    PencilPack *pp = (PencilPack *)lookup_handle(pack, H_PENCIL);
-    if (!pp) return -1;
-    PostSolve ps;
-    memset(&ps, 0, sizeof(ps));
-    return launch_matvec(pp, mat_id, x, y, ps, stream, 1);
-}
-
-int ddh_pencil_matvec_update_tiled(ddh_handle pack, int mat_id, const double *x, double *y, void *stream) {
-    PencilPack *pp = (PencilPack *)lookup_handle(pack, H_PENCIL);
-    if (!pp) return -1;
-    if (pp->dev.nf != 2 || (pp->dev.nx & 7) || (pp->dev.ny & 7))
-        return fail("pencil_matvec_update_tiled: two Fourier axes with storage sizes that are multiples of 8");
-    PostSolve ps;
-    memset(&ps, 0, sizeof(ps));
-    return launch_matvec(pp, mat_id, x, y, ps, stream, 1, 1);
+    return launch_matvec(pp, mat_id, x, y, ps, stream, tiled || (flags & DDH_MATVEC_OWNED), tiled);
 }
 
 int ddh_pencil_add_upper_bands(ddh_handle pack, int nz, int nbands, const int *offsets_h, const double *bands_h,
@@ -3887,37 +3873,6 @@ int ddh_pencil_set_block_inverse(ddh_handle pack, int lu_id, const double *binv_
     return 0;
 }
 
-int ddh_pencil_solve(ddh_handle pack, int lu_id, const double *rhs, double *x, void *stream) {
-    PencilPack *pp = (PencilPack *)lookup_handle(pack, H_PENCIL);
-    if (!pp) return -1;
-    if (lu_id < 0 || lu_id >= (int)pp->lus.size()) return fail("pencil_solve: bad LU id");
-    if (rhs == x) return fail("pencil_solve: in-place unsupported");
-    const double one = 1.0;
-    return ddh_pencil_solve_lincomb(pack, lu_id, 1, &rhs, &one, x, stream);
-}
-
-int ddh_pencil_solve_lincomb(ddh_handle pack, int lu_id, int nterms, const double *const *xs_h, const double *alpha_h,
-                             double *x, void *stream) {
-    PencilPack *pp = (PencilPack *)lookup_handle(pack, H_PENCIL);
-    if (!pp) return -1;
-    if (lu_id < 0 || lu_id >= (int)pp->lus.size()) return fail("pencil_solve: bad LU id");
-    if (nterms < 1 || nterms > RHS_MAX) return fail("pencil_solve_lincomb: 1 to 8 right-hand-side terms");
-    RhsSrc r;
-    memset(&r, 0, sizeof(r));
-    r.n = nterms;
-    for (int t = 0; t < nterms; ++t) {
-        if (xs_h[t] == x) return fail("pencil_solve: in-place unsupported");
-        r.p[t] = xs_h[t];
-        r.a[t] = alpha_h[t];
-    }
-    LuFactor *lu = pp->lus[lu_id];
-    hipStream_t s = as_stream(stream);
-    const SweepPlan pl = sweep_plan(pp, lu->dev, nterms, false);
-    if (pp->dev.nf == 2) return launch_solve<2>(pp, lu, r, x, s, pl);
-    if (pp->dev.nf == 1) return launch_solve<1>(pp, lu, r, x, s, pl);
-    return launch_solve<0>(pp, lu, r, x, s, pl);
-}
-
 // band table of the recombination matrix P (a registered constant real matrix) in the logical ordering of an LU;
 // returns 0 and leaves lu->dev.pband null when P cannot be fused (not unit upper banded within PBW, complex or
 // wavenumber-dependent entries, differing grading codes, border columns)
@@ -3993,36 +3948,6 @@ int ddh_pencil_set_mx_band(ddh_handle pack, int lu_id, int m_mat_id, int width, 
     return 0;
 }
 
-int ddh_pencil_solve_recombined(ddh_handle pack, int lu_id, int nterms, const double *const *xs_h,
-                                const double *alpha_h, int p_mat_id, double *work, double *x, void *stream) {
-    return ddh_pencil_solve_recombined_sparse(pack, lu_id, nterms, xs_h, alpha_h, p_mat_id, work, x, nullptr, nullptr, stream);
-}
-
-static int solve_recombined_impl(ddh_handle pack, int lu_id, int nterms, const double *const *xs_h, const double *alpha_h,
-                                 int p_mat_id, double *work, double *x, const unsigned char *zero_rows,
-                                 const unsigned char *skip_rows, int terms_tiled, void *stream, int m_mat_id = -1,
-                                 double *mx_out = nullptr);
-
-int ddh_pencil_solve_recombined_sparse(ddh_handle pack, int lu_id, int nterms, const double *const *xs_h,
-                                       const double *alpha_h, int p_mat_id, double *work, double *x,
-                                       const unsigned char *zero_rows, const unsigned char *skip_rows, void *stream) {
-    return solve_recombined_impl(pack, lu_id, nterms, xs_h, alpha_h, p_mat_id, work, x, zero_rows, skip_rows, 0, stream);
-}
-
-int ddh_pencil_solve_recombined_tiled(ddh_handle pack, int lu_id, int nterms, const double *const *xs_h,
-                                      const double *alpha_h, int p_mat_id, double *work, double *x,
-                                      const unsigned char *zero_rows, const unsigned char *skip_rows, void *stream) {
-    PencilPack *pp = (PencilPack *)lookup_handle(pack, H_PENCIL);
-    if (!pp) return -1;
-    if (lu_id < 0 || lu_id >= (int)pp->lus.size()) return fail("pencil_solve: bad LU id");
-    if (pp->dev.nf != 2 || (pp->dev.nx & 7) || (pp->dev.ny & 7))
-        return fail("pencil_solve_recombined_tiled: two Fourier axes with storage sizes that are multiples of 8");
-    if (!sweep_plan(pp, pp->lus[lu_id]->dev, nterms, false).lean_forward())
-        return fail("pencil_solve_recombined_tiled: this factorization does not run the lean forward sweep, the only one "
-                    "that reads tile-major terms (ddh_pencil_lu_info)");
-    return solve_recombined_impl(pack, lu_id, nterms, xs_h, alpha_h, p_mat_id, work, x, zero_rows, skip_rows, 1, stream);
-}
-
 // whether the sweeps of a tiled recombined solve of this factorization emit M.x, whatever the number of right-hand-side terms
 static int mx_emission(PencilPack *pp, LuFactor *lu, int p_mat_id, bool *emits) {
     *emits = false;
@@ -4044,67 +3969,85 @@ int ddh_pencil_lu_emits_mx(ddh_handle pack, int lu_id, int p_mat_id, int *emits)
     return 0;
 }
 
-int ddh_pencil_solve_recombined_tiled_mx(ddh_handle pack, int lu_id, int nterms, const double *const *xs_h,
-                                         const double *alpha_h, int p_mat_id, double *work, double *x,
-                                         const unsigned char *zero_rows, const unsigned char *skip_rows, int m_mat_id,
-                                         double *mx_out, void *stream) {
-    PencilPack *pp = (PencilPack *)lookup_handle(pack, H_PENCIL);
-    if (!pp) return -1;
+// A request checked against the pack and the factorization: the right-hand side, the kernels of the solve and the vector
+// the sweeps write (x itself, or `work` when x = P y follows as a mat-vec).  Nothing is launched here.
+static int check_solve(PencilPack *pp, int lu_id, const ddh_pencil_solve_req *q, RhsSrc *r, SweepPlan *pl, double **dest) {
+    if (!q || q->struct_size != sizeof(*q)) return fail("pencil_solve: request of another struct_size than this library's");
     if (lu_id < 0 || lu_id >= (int)pp->lus.size()) return fail("pencil_solve: bad LU id");
-    if (!mx_out || mx_out == x || mx_out == work) return fail("pencil_solve_recombined_tiled_mx: M.x needs a vector of its own");
-    bool e = false;
-    if (int st = mx_emission(pp, pp->lus[lu_id], p_mat_id, &e)) return st;
-    if (!e || !pp->lus[lu_id]->mx_ok || pp->lus[lu_id]->mx_mat != m_mat_id)
-        return fail("pencil_solve_recombined_tiled_mx: the sweeps of this factorization do not emit M.x "
-                    "(ddh_pencil_lu_emits_mx) or have no tables for this matrix (ddh_pencil_set_mx_band)");
-    return solve_recombined_impl(pack, lu_id, nterms, xs_h, alpha_h, p_mat_id, work, x, zero_rows, skip_rows, 1, stream,
-                                 m_mat_id, mx_out);
+    const bool want_p = q->p_mat_id >= 0, want_mx = q->m_mat_id >= 0;
+    if (q->p_mat_id >= (int)pp->mats.size() || q->m_mat_id >= (int)pp->mats.size()) return fail("pencil_solve: bad matrix id");
+    if (q->nterms < 1 || q->nterms > RHS_MAX) return fail("pencil_solve: 1 to 8 right-hand-side terms");
+    if (!want_p && (q->zero_rows || q->skip_rows)) return fail("pencil_solve: row masks need p_mat_id");
+    if (!want_p && q->terms_tiled) return fail("pencil_solve: tile-major terms need p_mat_id");
+    if (!want_p && want_mx) return fail("pencil_solve: M.x needs p_mat_id");
+    if (want_mx && !q->terms_tiled) return fail("pencil_solve: M.x needs tile-major terms");
+    if (want_p && (q->work == q->x || !q->work)) return fail("pencil_solve: work and x must be distinct buffers");
+    if (!want_mx && q->mx_out) return fail("pencil_solve: mx_out without m_mat_id");
+    if (want_mx && (!q->mx_out || q->mx_out == q->x || q->mx_out == q->work)) return fail("pencil_solve: M.x needs a vector of its own");
+    memset(r, 0, sizeof(*r));
+    r->n = q->nterms;
+    for (int t = 0; t < q->nterms; ++t) {
+        if (q->terms[t] == q->x || (want_p && q->terms[t] == q->work)) return fail("pencil_solve: in-place unsupported");
+        r->p[t] = q->terms[t];
+        r->a[t] = q->alpha[t];
+    }
+    r->zrow = q->zero_rows;
+    r->skip = q->skip_rows;
+    r->tiled = q->terms_tiled != 0;
+    LuFactor *lu = pp->lus[lu_id];
+    if (q->terms_tiled) {
+        if (pp->dev.nf != 2 || (pp->dev.nx & 7) || (pp->dev.ny & 7))
+            return fail("pencil_solve: tile-major terms need two Fourier axes with storage sizes that are multiples of 8");
+        if (!sweep_plan(pp, lu->dev, q->nterms, false).lean_forward())
+            return fail("pencil_solve: this factorization does not run the lean forward sweep, the only one that reads "
+                        "tile-major terms (ddh_pencil_lu_info)");
+    }
+    if (want_mx) {
+        bool e = false;
+        if (int st = mx_emission(pp, lu, q->p_mat_id, &e)) return st;
+        if (!e || !lu->mx_ok || lu->mx_mat != q->m_mat_id)
+            return fail("pencil_solve: the sweeps of this factorization do not emit M.x (ddh_pencil_lu_emits_mx) or have no "
+                        "tables for this matrix (ddh_pencil_set_mx_band)");
+    }
+    if (want_p && pp->dev.nf == 2)
+        if (int st = build_pband(pp, lu, q->p_mat_id)) return st;
+    *pl = sweep_plan(pp, lu->dev, q->nterms, want_p, want_mx);
+    // the fused kernel writes x directly; if the plan cannot fuse, the sweeps write the work vector instead
+    *dest = (want_p && !pl->fuse_p) ? q->work : q->x;
+    if (want_p && !pl->fuse_p) {
+        r->skip = nullptr;  // (the unfused path recombines from `work` with a mat-vec: every row of it must be written)
+        // (a tile-major state, ddh_pencil_set_state_tiled: `work` is written tile-major by the sweeps, and x must be too)
+        if (pp->dev.xtile == 2) return fail("pencil_solve: a kx-band-major state needs the fused recombination");
+    }
+    return 0;
 }
 
-static int solve_recombined_impl(ddh_handle pack, int lu_id, int nterms, const double *const *xs_h, const double *alpha_h,
-                                 int p_mat_id, double *work, double *x, const unsigned char *zero_rows,
-                                 const unsigned char *skip_rows, int terms_tiled, void *stream, int m_mat_id, double *mx_out) {
+int ddh_pencil_solve(ddh_handle pack, int lu_id, const ddh_pencil_solve_req *req, void *stream) {
     PencilPack *pp = (PencilPack *)lookup_handle(pack, H_PENCIL);
     if (!pp) return -1;
-    if (lu_id < 0 || lu_id >= (int)pp->lus.size()) return fail("pencil_solve: bad LU id");
-    if (p_mat_id < 0 || p_mat_id >= (int)pp->mats.size()) return fail("pencil_solve_recombined: bad matrix id");
-    if (nterms < 1 || nterms > RHS_MAX) return fail("pencil_solve_recombined: 1 to 8 right-hand-side terms");
-    if (work == x || !work) return fail("pencil_solve_recombined: work and x must be distinct buffers");
     RhsSrc r;
-    memset(&r, 0, sizeof(r));
-    r.n = nterms;
-    for (int t = 0; t < nterms; ++t) {
-        if (xs_h[t] == x || xs_h[t] == work) return fail("pencil_solve: in-place unsupported");
-        r.p[t] = xs_h[t];
-        r.a[t] = alpha_h[t];
-    }
-    r.zrow = zero_rows;
-    r.skip = skip_rows;
-    r.tiled = terms_tiled;
+    SweepPlan pl;
+    double *dest;
+    int st = check_solve(pp, lu_id, req, &r, &pl, &dest);
+    if (st) return st;
     LuFactor *lu = pp->lus[lu_id];
     hipStream_t s = as_stream(stream);
-    int st;
-    if (pp->dev.nf == 2 && (st = build_pband(pp, lu, p_mat_id))) return st;
-    // the fused kernel writes x directly; if the plan cannot fuse, the sweeps write the work vector instead
-    const SweepPlan pl = sweep_plan(pp, lu->dev, nterms, true, mx_out != nullptr);
-    if (pl.fuse_p) return launch_solve<2>(pp, lu, r, x, s, pl, m_mat_id, mx_out);
-    r.skip = nullptr;       // (the unfused path recombines from `work` with a mat-vec: every row of it must be written)
-    if (pp->dev.nf == 1 && lu->d_binv && lu->dev.real && lu->dev.n == lu->dev.nsplit * lu->dev.nh) {
+    if (pl.fuse_p) return launch_solve<2>(pp, lu, r, dest, s, pl, req->m_mat_id, req->mx_out);
+    const bool unfused_p = req->p_mat_id >= 0;          // the sweeps write `work` (dest), x = P work follows as a mat-vec
+    if (unfused_p && pp->dev.nf == 1 && lu->d_binv && lu->dev.real && lu->dev.n == lu->dev.nsplit * lu->dev.nh) {
         const LuDev &d = lu->dev;
         const unsigned nt = (unsigned)std::min(1024, (d.nh + 63) / 64 * 64);
         hipLaunchKernelGGL(blockinv_solve_kernel, dim3((unsigned)(pp->dev.ncells * d.nsplit)), dim3(nt), (size_t)d.nh * sizeof(double2),
-                           s, pp->dev, d, r, lu->d_binv, work);
+                           s, pp->dev, d, r, lu->d_binv, dest);
         DDH_HIP(hipGetLastError());
-        st = finish_solve<1>(pp, lu, r, work, s, 0);
-    } else if (pp->dev.nf == 2) st = launch_solve<2>(pp, lu, r, work, s, pl);
-    else if (pp->dev.nf == 1) st = launch_solve<1>(pp, lu, r, work, s, pl);
-    else st = launch_solve<0>(pp, lu, r, work, s, pl);
-    if (st) return st;
+        st = finish_solve<1>(pp, lu, r, dest, s, 0);
+    } else if (pp->dev.nf == 2) st = launch_solve<2>(pp, lu, r, dest, s, pl);
+    else if (pp->dev.nf == 1) st = launch_solve<1>(pp, lu, r, dest, s, pl);
+    else st = launch_solve<0>(pp, lu, r, dest, s, pl);
+    if (st || !unfused_p) return st;
     PostSolve none;
     memset(&none, 0, sizeof(none));
-    // (a tile-major state, ddh_pencil_set_state_tiled: `work` was written tile-major by the sweeps, and x must be too)
-    if (pp->dev.xtile == 2) return fail("pencil_solve_recombined: a kx-band-major state needs the fused recombination");
-    return launch_matvec(pp, p_mat_id, work, x, none, stream, 0, pp->dev.xtile);
+    return launch_matvec(pp, req->p_mat_id, dest, req->x, none, stream, 0, pp->dev.xtile);
 }
 
 int ddh_pencil_lu_row_widths(ddh_handle pack, int lu_id, int *wrow_h) {

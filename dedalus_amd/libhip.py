@@ -11,7 +11,8 @@ import os
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# (DDH_LIB: another build of the same library, for A/B timing of kernel variants)
+# (DDH_LIB: another build of the same library, for A/B timing of kernel variants; it must export every entry point of
+#  SIGNATURES, so it reaches back only as far as the request-based ddh_pencil_solve)
 LIB_PATH = os.environ.get("DDH_LIB") or os.path.join(_HERE, "csrc", "libdedalus_hip.so")
 
 _lib = None
@@ -40,6 +41,14 @@ class CflTerm(C.Structure):
                 ("comp_axis", C.c_int * 3), ("inv", C.c_void_p * 3), ("inv_h", C.c_double)]
 
 
+class PencilSolveReq(C.Structure):
+    """ddh_pencil_solve_req of include/dedalus_hip.h"""
+    _fields_ = [("struct_size", C.c_size_t), ("nterms", C.c_int), ("terms", C.c_void_p * 8), ("alpha", C.c_double * 8),
+                ("p_mat_id", C.c_int), ("work", C.c_void_p), ("x", C.c_void_p), ("zero_rows", C.c_void_p),
+                ("skip_rows", C.c_void_p), ("terms_tiled", C.c_int), ("m_mat_id", C.c_int), ("mx_out", C.c_void_p)]
+
+
+MATVEC_OWNED, MATVEC_TILED = 1, 2                                # DDH_MATVEC_* of include/dedalus_hip.h
 CFL_VELOCITY, CFL_SCALAR, CFL_SHELL, CFL_S2 = 0, 1, 2, 3         # DDH_CFL_* of include/dedalus_hip.h
 CFL_MAX_TERMS = 8
 
@@ -129,8 +138,7 @@ SIGNATURES = {
     "ddh_axis_contract_rows": [_vp, _vp, _l, _i, _l, _vp, _vp, _vp, _i, _vp],
     "ddh_pencil_create": [_hp, C.POINTER(PencilGeom)],
     "ddh_pencil_add_matrix": [_h, C.POINTER(PolyMat), _i, _ip],
-    "ddh_pencil_matvec": [_h, _i, _vp, _vp, _vp],
-    "ddh_pencil_matvec_update": [_h, _i, _vp, _vp, _vp],
+    "ddh_pencil_matvec": [_h, _i, _vp, _vp, _i, _vp],
     "ddh_pencil_add_upper_bands": [_h, _i, _i, _ip, _dp, _ip],
     "ddh_pencil_matvec_solve": [_h, _i, _i, _vp, _vp, _vp],
     "ddh_pencil_factor": [_h, _i, _i, _d, _d, _ip, _ip, _i, _i, _i,
@@ -138,18 +146,12 @@ SIGNATURES = {
     "ddh_pencil_factor_real": [_h, _i, _i, _d, _d, _ip, _ip, _i, _i, _i,
                                C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte),
                                C.POINTER(C.c_ubyte), _i, _ip, _vp],
-    "ddh_pencil_solve": [_h, _i, _vp, _vp, _vp],
+    "ddh_pencil_solve": [_h, _i, C.POINTER(PencilSolveReq), _vp],
     "ddh_pencil_set_solve_variant": [_h, _i, _i, _i],
     "ddh_pencil_set_pairing": [_h, _ip, _ip, _l],
     "ddh_pencil_set_row_blocks": [_h, _i],
-    "ddh_pencil_solve_lincomb": [_h, _i, _i, C.POINTER(_vp), _dp, _vp, _vp],
-    "ddh_pencil_solve_recombined": [_h, _i, _i, C.POINTER(_vp), _dp, _i, _vp, _vp, _vp],
-    "ddh_pencil_solve_recombined_sparse": [_h, _i, _i, C.POINTER(_vp), _dp, _i, _vp, _vp, _vp, _vp, _vp],
-    "ddh_pencil_solve_recombined_tiled": [_h, _i, _i, C.POINTER(_vp), _dp, _i, _vp, _vp, _vp, _vp, _vp],
-    "ddh_pencil_solve_recombined_tiled_mx": [_h, _i, _i, C.POINTER(_vp), _dp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp],
     "ddh_pencil_lu_emits_mx": [_h, _i, _i, _ip],
     "ddh_pencil_set_mx_band": [_h, _i, _i, _i, _ip, _dp],
-    "ddh_pencil_matvec_update_tiled": [_h, _i, _vp, _vp, _vp],
     "ddh_pencil_flagged": [_h, _i, _ip, C.POINTER(_l), _i],
     "ddh_pencil_set_dense_inverse": [_h, _i, _dp],
     "ddh_pencil_set_dense_inverse_dev": [_h, _i, _i, _vp, _i, _vp],
@@ -210,8 +212,6 @@ def load(build_if_missing=False):
                            "(there is no CPU fallback)" % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
     for name, argtypes in SIGNATURES.items():
-        if os.environ.get("DDH_LIB") and not hasattr(lib, name):
-            continue                     # an older experimental build: calling a missing entry point raises
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.argtypes = argtypes
         fn.restype = C.c_int

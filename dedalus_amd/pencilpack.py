@@ -98,21 +98,23 @@ class PencilPack:
 
     def matvec(self, mat_id, x, y, owned=False, tiled=False):
         """y = A x.  owned: y is a zero-initialised buffer that only this product writes (a timestepper's M.X vector): rows
-        without terms may then stay untouched (ddh_pencil_matvec_update).  tiled (with owned): y is written in the
-        tile-major layout the sweeps read contiguously (ddh_pencil_matvec_update_tiled)."""
+        without terms may then stay untouched (DDH_MATVEC_OWNED).  tiled (with owned): y is written in the
+        tile-major layout the sweeps read contiguously (DDH_MATVEC_TILED)."""
         t = self._timer()
         if t is not None:
             return t.run("pencil_matvec", (x.numel() + y.numel()) * 8, self._matvec, mat_id, x, y, owned, tiled)
         return self._matvec(mat_id, x, y, owned, tiled)
 
     def _matvec(self, mat_id, x, y, owned=False, tiled=False):
-        if tiled:
-            libhip.call("ddh_pencil_matvec_update_tiled", self.handle, mat_id, ptr(x), ptr(y), self.dev.stream)
-            return
-        libhip.call("ddh_pencil_matvec_update" if owned else "ddh_pencil_matvec", self.handle, mat_id, ptr(x), ptr(y),
-                    self.dev.stream)
+        flags = libhip.MATVEC_TILED if tiled else (libhip.MATVEC_OWNED if owned else 0)
+        libhip.call("ddh_pencil_matvec", self.handle, mat_id, ptr(x), ptr(y), flags, self.dev.stream)
 
+    # what core/solvers.py asks a pack before it chooses a path; the oracle's pack (oracle/np_executor.py) declares none of
+    # them and is driven step by step
     supports_tiled_rhs = True
+    supports_zero_rows = True
+    solves_requests = True          # `solve` takes the terms, P, the masks and M.x in one request
+    supports_mx_emission = True     # `emits_mx` / `set_mx_band` / solve(..., mx=)
 
     def set_state_tiled(self, on):
         """The vector every solve of this pack writes and every mat-vec of it reads (the solver's state X) is tile-major
@@ -271,83 +273,57 @@ class PencilPack:
 
     def set_block_inverse(self, lu_id, binv):
         """explicit transposed inverses [cell][block][k][i] of the diagonal blocks (device array, kept alive by the caller),
-        or None: ddh_pencil_solve_recombined* then applies them instead of running the sweeps"""
+        or None: a `solve` with p_mat_id then applies them instead of running the sweeps"""
         libhip.call("ddh_pencil_set_block_inverse", self.handle, int(lu_id), ptr(binv) if binv is not None else None)
         self.__dict__.setdefault("_binv_bytes", {})[int(lu_id)] = int(binv.numel()) * 8 if binv is not None else 0
 
-    def solve(self, lu_id, rhs, x):
-        t = self._timer()
-        if t is not None:
-            nb = self.lu_bytes(lu_id) + (rhs.numel() + x.numel()) * 8
-            return t.run("pencil_solve", nb, self._solve, lu_id, rhs, x)
-        return self._solve(lu_id, rhs, x)
-
-    def _solve(self, lu_id, rhs, x):
-        libhip.call("ddh_pencil_solve", self.handle, lu_id, ptr(rhs), ptr(x), self.dev.stream)
-
-    def solve_lincomb(self, lu_id, xs, alphas, x):
-        """x = (a M + b L)^-1 (sum_t alphas[t] xs[t]): the right-hand-side combination is formed inside the forward sweep
-        (ddh_pencil_solve_lincomb)."""
-        t = self._timer()
-        if t is not None:
-            nb = self.lu_bytes(lu_id) + (sum(v.numel() for v in xs) + x.numel()) * 8
-            return t.run("pencil_solve", nb, self._solve_lincomb, lu_id, xs, alphas, x)
-        return self._solve_lincomb(lu_id, xs, alphas, x)
-
-    def _solve_lincomb(self, lu_id, xs, alphas, x):
-        arr = (C.c_void_p * len(xs))(*[C.c_void_p(v.data_ptr()) for v in xs])
-        al = np.ascontiguousarray(alphas, dtype=np.float64)
-        libhip.call("ddh_pencil_solve_lincomb", self.handle, lu_id, len(xs), arr, libhip.as_dp(al), ptr(x), self.dev.stream)
-
-    supports_zero_rows = True
-
-    def solve_recombined(self, lu_id, xs, alphas, p_mat_id, work, x, zero_rows=None, skip_rows=None, tiled=False, mx=None):
-        """x = P (a M + b L P)^-1 (sum_t alphas[t] xs[t]) (ddh_pencil_solve_recombined): recombination fused into the
-        backward sweep where the kernel variant allows, else through `work` and a mat-vec.
+    def solve(self, lu_id, xs, alphas, x, p_mat_id=None, work=None, zero_rows=None, skip_rows=None, tiled=False, mx=None):
+        """x = (a M + b L)^-1 (sum_t alphas[t] xs[t]), the combination formed inside the forward sweep; with p_mat_id,
+        x = P (a M + b L P)^-1 (...): the recombination fused into the backward sweep where the kernel variant allows, else
+        through `work` and a mat-vec.  One ddh_pencil_solve_req (include/dedalus_hip.h) per call; the rest needs p_mat_id:
         zero_rows = (device uint8 mask, fraction set): rows that are zero in every term; skip_rows = (mask, fraction):
-        unknowns the caller does not need (ddh_pencil_solve_recombined_sparse).
-        mx = (mass matrix id, tile-major destination): the backward sweep also writes M x there
-        (ddh_pencil_solve_recombined_tiled_mx; only where `emits_mx` says so, with tiled terms)."""
+        unknowns the caller does not need.  tiled: the terms are tile-major.
+        mx = (mass matrix id, tile-major destination): the backward sweep also writes M x there (only where `emits_mx`
+        says so, with tiled terms)."""
         t = self._timer()
-        if t is not None and mx is not None:
-            # the factors, the terms and x as below, plus the rows of M.x the sweep writes
-            info = self.lu_info(lu_id)
-            read = 1.0 - (zero_rows[1] if (zero_rows is not None and info["forward"] == "lean") else 0.0)
+        if t is not None:
+            nb = self.solve_bytes(lu_id, xs, x, p_mat_id, zero_rows, skip_rows, mx)
+            return t.run("pencil_solve", nb, self._solve, lu_id, xs, alphas, x, p_mat_id, work, zero_rows, skip_rows, tiled, mx)
+        return self._solve(lu_id, xs, alphas, x, p_mat_id, work, zero_rows, skip_rows, tiled, mx)
+
+    def solve_bytes(self, lu_id, xs, x, p_mat_id=None, zero_rows=None, skip_rows=None, mx=None):
+        """Algorithmic HBM bytes of one `solve` for the timer: the factors, the terms and x.  tools/bench_configs.py and the
+        roofline fractions of DESIGN.md derive from these numbers, so they are outputs (tests/test_pencil_request_host.py)."""
+        terms = sum(v.numel() for v in xs)
+        if p_mat_id is None:
+            return self.lu_bytes(lu_id) + (terms + x.numel()) * 8
+        info = self.lu_info(lu_id)          # masked rows are not read / written -- by the kernels that honour the masks
+        read = 1.0 - (zero_rows[1] if (zero_rows is not None and info["forward"] == "lean") else 0.0)
+        if mx is not None:                  # plus the rows of M.x the sweep writes
             wrote = 1.0 - (skip_rows[1] if skip_rows is not None else 0.0)
             mrows = len(np.unique(np.asarray(self.matrices[mx[0]].row)))
-            nb = self.lu_bytes(lu_id) + (sum(v.numel() for v in xs) * read + x.numel() * wrote
-                                         + mx[1].numel() * mrows / float(self.nrows)) * 8
-            return t.run("pencil_solve", nb, self._solve_recombined, lu_id, xs, alphas, p_mat_id, work, x, zero_rows,
-                         skip_rows, tiled, mx)
-        if t is not None:
-            info = self.lu_info(lu_id)          # masked rows are not read / written -- by the kernels that honour the masks
-            read = 1.0 - (zero_rows[1] if (zero_rows is not None and info["forward"] == "lean") else 0.0)
-            wrote = 1.0 - (skip_rows[1] if (skip_rows is not None and info["backward_lanes"] == 0 and info["real"]) else 0.0)
-            nb = self.lu_bytes(lu_id) + (sum(v.numel() for v in xs) * read + x.numel() * wrote) * 8
-            binv = getattr(self, "_binv_bytes", {}).get(lu_id)
-            if binv:                            # explicit block inverses: they are what the solve streams, not the factors
-                nb = binv + (sum(v.numel() for v in xs) + 3 * x.numel()) * 8      # (+ work written, read by the P mat-vec, x written)
-            return t.run("pencil_solve", nb, self._solve_recombined, lu_id, xs, alphas, p_mat_id, work, x, zero_rows,
-                         skip_rows, tiled)
-        return self._solve_recombined(lu_id, xs, alphas, p_mat_id, work, x, zero_rows, skip_rows, tiled, mx)
+            return self.lu_bytes(lu_id) + (terms * read + x.numel() * wrote + mx[1].numel() * mrows / float(self.nrows)) * 8
+        binv = getattr(self, "_binv_bytes", {}).get(lu_id)
+        if binv:                            # explicit block inverses: they are what the solve streams, not the factors
+            return binv + (terms + 3 * x.numel()) * 8      # (+ work written, read by the P mat-vec, x written)
+        wrote = 1.0 - (skip_rows[1] if (skip_rows is not None and info["backward_lanes"] == 0 and info["real"]) else 0.0)
+        return self.lu_bytes(lu_id) + (terms * read + x.numel() * wrote) * 8
 
-    def _solve_recombined(self, lu_id, xs, alphas, p_mat_id, work, x, zero_rows=None, skip_rows=None, tiled=False, mx=None):
-        arr = (C.c_void_p * len(xs))(*[C.c_void_p(v.data_ptr()) for v in xs])
-        al = np.ascontiguousarray(alphas, dtype=np.float64)
-        if zero_rows is not None or skip_rows is not None or tiled:
-            zp = C.c_void_p(zero_rows[0].data_ptr()) if zero_rows is not None else None
-            sp = C.c_void_p(skip_rows[0].data_ptr()) if skip_rows is not None else None
-            if mx is not None:
-                if not tiled:
-                    raise ValueError("M.x from the sweep needs tile-major terms")
-                libhip.call("ddh_pencil_solve_recombined_tiled_mx", self.handle, lu_id, len(xs), arr, libhip.as_dp(al),
-                            int(p_mat_id), ptr(work), ptr(x), zp, sp, int(mx[0]), ptr(mx[1]), self.dev.stream)
-                return
-            libhip.call("ddh_pencil_solve_recombined_tiled" if tiled else "ddh_pencil_solve_recombined_sparse", self.handle,
-                        lu_id, len(xs), arr, libhip.as_dp(al), int(p_mat_id), ptr(work), ptr(x), zp, sp, self.dev.stream)
-            return
-        libhip.call("ddh_pencil_solve_recombined", self.handle, lu_id, len(xs), arr, libhip.as_dp(al), int(p_mat_id),
-                    ptr(work), ptr(x), self.dev.stream)
+    def _solve(self, lu_id, xs, alphas, x, p_mat_id=None, work=None, zero_rows=None, skip_rows=None, tiled=False, mx=None):
+        q = libhip.PencilSolveReq()
+        q.struct_size = C.sizeof(q)
+        q.nterms = n = len(xs)              # (the library refuses what does not fit the struct: 1 .. MAX_RHS_TERMS)
+        for i in range(min(n, self.MAX_RHS_TERMS)):
+            q.terms[i] = xs[i].data_ptr()
+            q.alpha[i] = alphas[i]
+        q.p_mat_id = -1 if p_mat_id is None else int(p_mat_id)
+        q.work = work.data_ptr() if work is not None else None
+        q.x = x.data_ptr()
+        q.zero_rows = zero_rows[0].data_ptr() if zero_rows is not None else None
+        q.skip_rows = skip_rows[0].data_ptr() if skip_rows is not None else None
+        q.terms_tiled = bool(tiled)
+        q.m_mat_id, q.mx_out = (-1, None) if mx is None else (int(mx[0]), mx[1].data_ptr())
+        libhip.call("ddh_pencil_solve", self.handle, lu_id, C.byref(q), self.dev.stream)
 
     MAX_RHS_TERMS = 8
 
@@ -383,8 +359,6 @@ class PencilPack:
     def emits_mx(self, lu_id, p_mat_id):
         """Whether the sweeps of a tiled recombined solve of this factorization can write M x (ddh_pencil_lu_emits_mx:
         the kernels only; the tables come from `set_mx_band`); depends on the sweep variant, like lu_info."""
-        if not hasattr(libhip.load(), "ddh_pencil_lu_emits_mx"):
-            return False                    # (DDH_LIB: an older build of the library, for A/B timing)
         v = C.c_int(0)
         libhip.call("ddh_pencil_lu_emits_mx", self.handle, int(lu_id), int(p_mat_id), C.byref(v))
         return bool(v.value)

@@ -112,7 +112,7 @@ int ddh_cheb_forward(ddh_handle plan, const double *g, double *c, long outer, lo
 /* The same transform with the coefficient rows written TILE-MAJOR: a row of `inner` = nx * row_len doubles is stored as
  * [kx / 8][ky / 8][kx % 8][ky % 8] (64-byte segments of a tile of 8 storage rows x 8 doubles contiguous) instead of
  * [kx][ky].  It is the layout the pencil sweeps read with two contiguous 512-byte runs per wavefront and row
- * (ddh_pencil_solve_recombined_tiled); the forward transform of a right-hand-side product writes the equation rows of the
+ * (ddh_pencil_solve_req::terms_tiled); the forward transform of a right-hand-side product writes the equation rows of the
  * solver's F vector directly in it.  Values are those of ddh_cheb_forward (core/transforms.py:801-902), only their
  * addresses differ.  nx and row_len multiples of 8; strided-axis wave kernel sizes only (N = 384, M = 256), an error
  * otherwise; not in place.                                                                                            */
@@ -485,13 +485,18 @@ int ddh_pencil_create(ddh_handle *pack, const ddh_pencil_geom *geom);
 /* register a matrix; returns its id in *mat_id */
 int ddh_pencil_add_matrix(ddh_handle pack, const ddh_polymat *mat, int nrows_out, int *mat_id);
 /* y[nrows_out][cells] = A x  (apply_sparse tools/array.py:171-203 over all pencils at once;
- * gather/scatter subsystems.py:340-380 are the identity in this layout)                           */
-int ddh_pencil_matvec(ddh_handle pack, int mat_id, const double *x, double *y, void *stream);
-/* The same for a buffer the caller keeps for this product alone (the M.X vectors of a timestepper, core/timesteppers.py:588-591
- * with its CoeffSystem buffers core/system.py:39-60, zero-initialised): rows of
- * y whose matrix row has no terms MAY be left untouched instead of being overwritten with zeros (the window-form kernel
- * skips those stores; a fifth of M.X for an incompressible flow).  Every other row is written as by ddh_pencil_matvec.  */
-int ddh_pencil_matvec_update(ddh_handle pack, int mat_id, const double *x, double *y, void *stream);
+ * gather/scatter subsystems.py:340-380 are the identity in this layout)
+ * flags:
+ *   DDH_MATVEC_OWNED  y is a buffer the caller keeps for this product alone (the M.X vectors of a timestepper,
+ *                     core/timesteppers.py:588-591 with its CoeffSystem buffers core/system.py:39-60, zero-initialised): rows of
+ *                     y whose matrix row has no terms MAY be left untouched instead of being overwritten with zeros (the
+ *                     window-form kernel skips those stores; a fifth of M.X for an incompressible flow).  Every other row is
+ *                     written as without the flag.
+ *   DDH_MATVEC_TILED  (implies OWNED) y is written tile-major, see ddh_pencil_solve_req::terms_tiled (window-form matrices
+ *                     only: the timesteppers' M.X products; two Fourier axes, nx and ny multiples of 8); x in the layout of
+ *                     the state (ddh_pencil_set_state_tiled)                                                           */
+enum { DDH_MATVEC_OWNED = 1, DDH_MATVEC_TILED = 2 };
+int ddh_pencil_matvec(ddh_handle pack, int mat_id, const double *x, double *y, int flags, void *stream);
 /* Mat-vec fused with an upper-banded back-substitution along the coupled index of every output
  * component (rows = (component, kz), nz per component): y <- C^-1 (A x).  With C the ultraspherical
  * conversion matrix this yields the coefficients directly in the grid (Chebyshev-T) basis, i.e. the
@@ -525,31 +530,69 @@ int ddh_pencil_factor_real(ddh_handle pack, int matM_id, int matL_id, double a, 
                            const unsigned char *row_axes_h, const unsigned char *col_axes_h,
                            const unsigned char *row_code_h, const unsigned char *col_code_h,
                            int reuse_lu_id, int *lu_id, void *stream);
-int ddh_pencil_solve(ddh_handle pack, int lu_id, const double *rhs, double *x, void *stream);
-/* Solve with the right-hand side given as a linear combination rhs = sum_t alpha[t] * xs[t] of stored system vectors
- * (1 <= nterms <= 8): the RHS assembly of the IMEX schemes (timesteppers.py:156-166, 617-623: an axpy chain into a RHS
- * buffer, then LHS_solver.solve) fused into the forward sweep -- the combined vector is never written to or re-read
- * from HBM.  xs_h: host array of device pointers; none may alias x.                                              */
-int ddh_pencil_solve_lincomb(ddh_handle pack, int lu_id, int nterms, const double *const *xs_h, const double *alpha_h,
-                             double *x, void *stream);
-/* x = P (a M + b L P)^-1 rhs: the solve of the column-recombined system (X = P Y makes the
- * boundary rows sparse) including the recombination.  p_mat_id: the registered constant matrix P.  When P is unit upper
- * banded in the LU's ordering (the Dirichlet / Neumann recombinations are) and the one-thread-per-system backward
- * sweep runs, x_j = y_j + sum_d P[j, j+d] y_(j+d) is formed from the sweep's register window and written directly --
- * neither y nor a separate P.y mat-vec touch HBM; otherwise y goes to `work` and ddh_pencil_matvec(P) follows.
- * work: a system vector of scratch, distinct from x and the right-hand-side terms.                                */
-int ddh_pencil_solve_recombined(ddh_handle pack, int lu_id, int nterms, const double *const *xs_h,
-                                const double *alpha_h, int p_mat_id, double *work, double *x, void *stream);
-/* The same with a row mask: zero_rows[r] != 0 (device array, one byte per row of the system vectors) promises that row r is
- * zero in EVERY right-hand-side term -- rows of equations without time derivative and without right-hand side (the
- * continuity equation of core/timesteppers.py:588-623's M.X / F vectors).  The forward sweep then does not read them
- * (a fifth of the right-hand-side traffic of 3-D Rayleigh-Benard).  Kernels without the shortcut ignore the mask, which
- * is always correct.  skip_rows[r] != 0 (same shape, rows of the SOLUTION): the caller does not need unknown r of x -- an
- * intermediate Runge-Kutta stage never reads the pressure and the tau variables (no mass-matrix column, not an operand of F)
- * -- and the backward sweep does not store it; x keeps whatever it held there.  null masks = ddh_pencil_solve_recombined. */
-int ddh_pencil_solve_recombined_sparse(ddh_handle pack, int lu_id, int nterms, const double *const *xs_h,
-                                       const double *alpha_h, int p_mat_id, double *work, double *x,
-                                       const unsigned char *zero_rows, const unsigned char *skip_rows, void *stream);
+/* One solve of a factorization, described by a request.  A request is checked completely before anything is launched; a
+ * combination of fields the kernels do not serve is an error, never another path.
+ *   struct_size        sizeof(ddh_pencil_solve_req) of the caller: a library built from another header refuses the request
+ *   nterms, terms,     the right-hand side as a linear combination rhs = sum_t alpha[t] * terms[t] of stored system vectors
+ *   alpha              (1 <= nterms <= 8 device vectors): the RHS assembly of the IMEX schemes (timesteppers.py:156-166,
+ *                      617-623: an axpy chain into a RHS buffer, then LHS_solver.solve) fused into the forward sweep -- the
+ *                      combined vector is never written to or re-read from HBM.  No term may alias x.
+ *   p_mat_id           -1: x = (a M + b L)^-1 rhs.  >= 0: x = P (a M + b L P)^-1 rhs, the solve of the column-recombined
+ *                      system (X = P Y makes the boundary rows sparse) including the recombination, P
+ *                      the registered constant matrix of that id.  When P is unit upper banded in the LU's ordering (the
+ *                      Dirichlet / Neumann recombinations are) and the one-thread-per-system backward sweep runs, x_j =
+ *                      y_j + sum_d P[j, j+d] y_(j+d) is formed from the sweep's register window and written directly --
+ *                      neither y nor a separate P.y mat-vec touch HBM; otherwise y goes to `work` and ddh_pencil_matvec(P)
+ *                      follows.  The fields below need p_mat_id >= 0.
+ *   work               with p_mat_id >= 0: a system vector of scratch, distinct from x and the right-hand-side terms
+ *   x                  the solution, in the layout of the state (ddh_pencil_set_state_tiled)
+ *   zero_rows          null, or a device array of one byte per row of the system vectors: zero_rows[r] != 0 promises that
+ *                      row r is zero in EVERY right-hand-side term -- rows of equations without time derivative and without
+ *                      right-hand side (the continuity equation of core/timesteppers.py:588-623's M.X / F vectors).  The
+ *                      forward sweep then does not read them (a fifth of the right-hand-side traffic of 3-D
+ *                      Rayleigh-Benard).  Kernels without the shortcut ignore the mask, which is always correct.
+ *   skip_rows          null, or the same shape over the rows of the SOLUTION: skip_rows[r] != 0, the caller does not need
+ *                      unknown r of x -- an intermediate Runge-Kutta stage never reads the pressure and the tau variables (no
+ *                      mass-matrix column, not an operand of F) -- and the backward sweep does not store it; x keeps
+ *                      whatever it held there.
+ *   terms_tiled        != 0: the term vectors are ALL tile-major (two Fourier axes, nx and ny multiples of 8); x (the state)
+ *                      and work keep their layout.  The sweeps hand a wavefront the 16 cells of a 4 x 4 tile and of its
+ *                      transposed partner tile; in the natural row layout [nx][ny] its 64 accesses to a row of a system
+ *                      vector are sixteen 64-byte runs in eight storage rows, in the tile-major layout
+ *                      [kx/8][ky/8][kx%8][ky%8] two contiguous 512-byte runs (measured: -1.4 ms of a 6.8 ms solve at 512 x
+ *                      512 x 256 with contiguous term reads).  Needs the lean forward sweep (ddh_pencil_lu_info), an error
+ *                      otherwise.  The reference gathers every pencil's right-hand side into a dense buffer
+ *                      (core/subsystems.py:340-380); the values and the linear systems are the same, only the addresses of
+ *                      the solver-internal vectors differ.
+ *   m_mat_id, mx_out   -1 and null, or M.x from the backward sweep (needs terms_tiled).  A Runge-Kutta step needs M.X of
+ *                      the state a solve has just written (the next stage's right-hand side, core/timesteppers.py:588-604):
+ *                      a DDH_MATVEC_TILED product reads that state back from HBM.  With the recombination fused, the
+ *                      one-thread-per-system backward sweep holds y_j .. y_(j+17) of x = P y in registers when row j is
+ *                      done, and every row of the band of M P (M real and wavenumber independent: conversions between
+ *                      polynomial bases) fits that window: the full-size sweep writes (M x)[row] = sum_d (M P)[row, j + d]
+ *                      y_(j+d) itself, tile-major, into mx_out.  m_mat_id: the physical mass matrix (with partner pencils
+ *                      it must share their symmetry).  Rows of M without terms are not written (mx_out is a persistent,
+ *                      zeroed buffer, as for DDH_MATVEC_OWNED); unknowns masked by skip_rows still enter the product; flagged
+ *                      pencils get theirs from their dense solution.  mx_out may be one of the right-hand-side terms (they
+ *                      are consumed before the backward sweep) but not x or work.  An error when the sweeps of the
+ *                      factorization do not emit (ddh_pencil_lu_emits_mx) or have no tables for m_mat_id
+ *                      (ddh_pencil_set_mx_band).  The reference forms M.X with a sparse product per subproblem
+ *                      (core/timesteppers.py:588-604); the values agree to the round-off of a different summation order. */
+typedef struct {
+    size_t struct_size;
+    int nterms;
+    const double *terms[8];
+    double alpha[8];
+    int p_mat_id;
+    double *work;
+    double *x;
+    const unsigned char *zero_rows;
+    const unsigned char *skip_rows;
+    int terms_tiled;
+    int m_mat_id;
+    double *mx_out;
+} ddh_pencil_solve_req;
+int ddh_pencil_solve(ddh_handle pack, int lu_id, const ddh_pencil_solve_req *req, void *stream);
 /* Sweep variant used by ddh_pencil_solve (all variants compute the same factorization's solution; they differ in how
  * many lanes share one system).  mode 1 (default): chosen by the number of systems; 0: one
  * thread per system; 2: cooperative (16 lanes) in both sweeps.  fwd = 0 / 1 and backward_lanes = 0 / 4 / 16 override
@@ -570,49 +613,16 @@ int ddh_pencil_set_solve_variant(ddh_handle pack, int mode, int fwd, int backwar
  * symmetry on its term lists); NULL, NULL switches pairing off.  Needs the real-graded factorization
  * (ddh_pencil_factor_real), two Fourier axes, a square unsharded cell grid with kx_h == ky_h; otherwise ignored.   */
 int ddh_pencil_set_pairing(ddh_handle pack, const int *row_swap_h, const int *col_swap_h, long min_systems);
-/* Tile-major right-hand-side vectors (two Fourier axes, nx and ny multiples of 8).  The sweeps hand a wavefront the 16
- * cells of a 4 x 4 tile and of its transposed partner tile; in the natural row layout [nx][ny] its 64 accesses to a row
- * of a system vector are sixteen 64-byte runs in eight storage rows, in the tile-major layout [kx/8][ky/8][kx%8][ky%8]
- * two contiguous 512-byte runs (measured: -1.4 ms of a 6.8 ms solve at 512 x 512 x 256 with contiguous term reads).
- *   ddh_pencil_matvec_update_tiled      y = A x like ddh_pencil_matvec_update, y written tile-major (window-form
- *                                       matrices only: the timesteppers' M.X products); x in the natural layout
- *   ddh_pencil_solve_recombined_tiled   ddh_pencil_solve_recombined_sparse whose term vectors xs_h are ALL tile-major;
- *                                       x (the state) and work keep the natural layout.  Needs the lean forward sweep
- *                                       (ddh_pencil_lu_info), an error otherwise.
- * The reference gathers every pencil's right-hand side into a dense buffer (core/subsystems.py:340-380); the values and
- * the linear systems are the same, only the addresses of the solver-internal vectors differ.                          */
-int ddh_pencil_matvec_update_tiled(ddh_handle pack, int mat_id, const double *x, double *y, void *stream);
-int ddh_pencil_solve_recombined_tiled(ddh_handle pack, int lu_id, int nterms, const double *const *xs_h,
-                                      const double *alpha_h, int p_mat_id, double *work, double *x,
-                                      const unsigned char *zero_rows, const unsigned char *skip_rows, void *stream);
-/* M.x from the backward sweep.  A Runge-Kutta step needs M.X of the state a solve has just written (the next stage's
- * right-hand side, core/timesteppers.py:588-604): ddh_pencil_matvec_update_tiled reads that state back from HBM.  With
- * the recombination fused, the one-thread-per-system backward sweep holds y_j .. y_(j+17) of x = P y in registers when row j
- * is done, and every row of the band of M P (M real and wavenumber independent: conversions between polynomial bases) fits
- * that window: the full-size sweep writes (M x)[row] = sum_d (M P)[row, j + d] y_(j+d) itself, tile-major, into mx_out.
- *   ddh_pencil_solve_recombined_tiled_mx  ddh_pencil_solve_recombined_tiled + mx_out = M x for the matrix m_mat_id (the
- *                                         physical mass matrix; with partner pencils it must share their symmetry).  Rows
- *                                         of M without terms are not written (mx_out is a persistent, zeroed buffer, as for
- *                                         ddh_pencil_matvec_update*); unknowns masked by skip_rows still enter the product;
- *                                         flagged pencils get theirs from their dense solution.  mx_out may be one of the
- *                                         right-hand-side terms (they are consumed before the backward sweep).  An error
- *                                         when the sweeps of the factorization do not emit:
- *   ddh_pencil_lu_emits_mx                *emits = 1 when the kernels can, for any number of right-hand-side terms --
- *                                         the lean forward sweep and the one-thread-per-(system, block) backward sweep
- *                                         with the fused recombination and a window of 17 (not the deep, cooperative or
- *                                         block-inverse paths), tile-able sizes.  Depends on ddh_pencil_set_solve_variant.
- *   ddh_pencil_set_mx_band                the host's analysis of M P in the ordering of the factorization (the caller has
- *                                         the graded term lists; with partner pencils M P must share their symmetry):
- *                                         step_row_h[j] (n ints) = the logical equation row formed when row j of the
- *                                         sweep is done, -1 none; band_h[j * width + d] = (M P)[step_row_h[j], j + d],
- *                                         width = 18.  Checked here: every row at most once, no entry beyond the band
- *                                         rows or outside the diagonal block of its step.  Needed before the solve.
- * The reference forms M.X with a sparse product per subproblem (core/timesteppers.py:588-604); the values agree to the
- * round-off of a different summation order.                                                                            */
-int ddh_pencil_solve_recombined_tiled_mx(ddh_handle pack, int lu_id, int nterms, const double *const *xs_h,
-                                         const double *alpha_h, int p_mat_id, double *work, double *x,
-                                         const unsigned char *zero_rows, const unsigned char *skip_rows, int m_mat_id,
-                                         double *mx_out, void *stream);
+/* What a request with m_mat_id >= 0 (ddh_pencil_solve_req) needs beforehand:
+ *   ddh_pencil_lu_emits_mx   *emits = 1 when the kernels can, for any number of right-hand-side terms -- the lean forward
+ *                            sweep and the one-thread-per-(system, block) backward sweep with the fused recombination and
+ *                            a window of 17 (not the deep, cooperative or block-inverse paths), tile-able sizes.  Depends
+ *                            on ddh_pencil_set_solve_variant.
+ *   ddh_pencil_set_mx_band   the host's analysis of M P in the ordering of the factorization (the caller has the graded
+ *                            term lists; with partner pencils M P must share their symmetry): step_row_h[j] (n ints) = the
+ *                            logical equation row formed when row j of the sweep is done, -1 none; band_h[j * width + d] =
+ *                            (M P)[step_row_h[j], j + d], width = 18.  Checked here: every row at most once, no entry
+ *                            beyond the band rows or outside the diagonal block of its step.                            */
 int ddh_pencil_lu_emits_mx(ddh_handle pack, int lu_id, int p_mat_id, int *emits);
 int ddh_pencil_set_mx_band(ddh_handle pack, int lu_id, int m_mat_id, int width, const int *step_row_h, const double *band_h);
 /* Independent diagonal blocks.  When the band block of the ordered pencil matrix (rows / columns < n_interior of
@@ -638,13 +648,13 @@ int ddh_pencil_set_dense_inverse(ddh_handle pack, int lu_id, const double *inv_h
 int ddh_pencil_set_dense_inverse_dev(ddh_handle pack, int lu_id, int sys, const double *inv_d, int is_complex, void *stream);
 /* Few systems with one Fourier axis (2-D problems): explicit inverses of the independent diagonal blocks of a real-graded
  * factorization (ddh_pencil_set_row_blocks; nblocks = 1: the whole band block), TRANSPOSED -- binv_d [cell][block][k][i] =
- * (block^-1)[i][k], caller-owned device memory, formed e.g. by unit solves of ddh_ellband_* -- make ddh_pencil_solve_recombined*
+ * (block^-1)[i][k], caller-owned device memory, formed e.g. by unit solves of ddh_ellband_* -- make a ddh_pencil_solve with p_mat_id
  * apply them as streaming GEMVs instead of running the sweeps (a chain of n / nblocks dependent rows that a few hundred
  * systems cannot hide).  The solutions are those of the same systems the reference factors per subproblem
  * (libraries/matsolvers.py:126-149).  Border unknowns must exist for flagged pencils only.  binv_d = NULL: back to the sweeps. */
 int ddh_pencil_set_block_inverse(ddh_handle pack, int lu_id, const double *binv_d);
 int ddh_pencil_lu_bytes(ddh_handle pack, int lu_id, size_t *bytes);
-/* Shape of a factorization and the sweep kernels ddh_pencil_solve* will launch for it (diagnostics, byte accounting,
+/* Shape of a factorization and the sweep kernels ddh_pencil_solve will launch for it (diagnostics, byte accounting,
  * tests): info_h[12] = { n (band rows), nb (border), kl, ku, W = kl + ku, BW (stored entries per band row), nsplit
  * (independent diagonal blocks swept by separate threads, ddh_pencil_set_row_blocks), rows per block, forward sweep
  * (0 general one-thread-per-system, 1 lean one-thread-per-system -- the one that honours zero_rows --, 2 cooperative),

@@ -44,7 +44,7 @@ class ReferencePencils:
 
     def check(self, g, a, b, rhs_gathered, x_gathered, solve=True, skipped=None):
         """skipped (bool per gathered unknown, or None): unknowns the solve did NOT store (intermediate Runge-Kutta stages
-        leave out what nothing reads before the last stage, ddh_pencil_solve_recombined_sparse): the stored ones are
+        leave out what nothing reads before the last stage, ddh_pencil_solve_req::skip_rows): the stored ones are
         compared with the reference's SuperLU solution, and the residual is that of the stored unknowns completed by the
         reference's values for the others."""
         m = self.data[g]

@@ -316,7 +316,7 @@ def test_reference_style_loop_loses_no_output(tmp_path):
 
 def test_zero_row_mask_of_the_runge_kutta_right_hand_side(monkeypatch):
     """Rows that are zero in M.X and in F (the continuity equation) are not read by the lean forward sweep
-    (ddh_pencil_solve_recombined_sparse): same end state bit for bit as with the mask switched off, and the mask is what
+    (ddh_pencil_solve_req::zero_rows): same end state bit for bit as with the mask switched off, and the mask is what
     the problem structure says."""
     import dedalus_amd.public as d3
 
@@ -380,8 +380,8 @@ def test_unknowns_skipped_by_intermediate_stages_are_never_consumed(monkeypatch)
 
 
 def test_tile_major_right_hand_sides_change_addresses_not_values(monkeypatch):
-    """The timestepper's M.X and F buffers in the tile-major layout (ddh_pencil_matvec_update_tiled,
-    ddh_cheb_forward_tiled, ddh_pencil_solve_recombined_tiled) against the natural layout (DDH_NO_RHS_TILING): the same
+    """The timestepper's M.X and F buffers in the tile-major layout (DDH_MATVEC_TILED,
+    ddh_cheb_forward_tiled, ddh_pencil_solve_req::terms_tiled) against the natural layout (DDH_NO_RHS_TILING): the same
     values are summed in the same order, so the end states agree bit for bit.  256 x 256 x 256: the smallest size at which
     every tiled producer runs (window mat-vec, strided wave transform, lean sweep)."""
     import dedalus_amd.public as d3
@@ -408,9 +408,9 @@ def test_tile_major_right_hand_sides_change_addresses_not_values(monkeypatch):
 def test_tile_major_layout_follows_the_sweep_variant(monkeypatch):
     """The tile-major decision belongs to the factorizations and the sweep variant of the moment (SolverBase.rhs_tiling is
     asked again after PencilPack.set_solve_variant and after every refactorization): a solver that starts tiled and is
-    switched to the cooperative sweeps (no tiled form) goes back to the natural layout instead of failing inside
-    ddh_pencil_solve_recombined_tiled, returns to tile-major with the default variant, and reaches bit for bit the end state
-    of a run that never tiled."""
+    switched to the cooperative sweeps (no tiled form) goes back to the natural layout instead of failing inside a
+    ddh_pencil_solve with terms_tiled, returns to tile-major with the default variant, and reaches bit for bit the end
+    state of a run that never tiled."""
     import dedalus_amd.public as d3
 
     def run(tiled):

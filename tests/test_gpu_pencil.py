@@ -162,7 +162,7 @@ def test_matvec_factor_solve_vs_oracle(nf, ncx, ncy, gauge, coop):
             rhs[r, 0, 0] = keep
     drhs = dev.from_host(rhs)
     dsol = dev.empty((N, nx, ny))
-    pack.solve(lu, drhs, dsol)
+    pack.solve(lu, [drhs], [1.0], dsol)
     dev.sync()
     ref = npp.PencilLU(Mo, Lo, a, b, nf, nx, ny, kx, ky, pb["row_axes"], pb["col_axes"]).solve(rhs)
     sol = dev.to_host(dsol)
@@ -184,7 +184,7 @@ def test_matvec_factor_solve_vs_oracle(nf, ncx, ncy, gauge, coop):
     # re-factor in place with a different coefficient (dt change) and solve again
     lu2 = pack.factor(idM, idL, a, 0.11, pb["perm"], pb["perm"], n, kl, ku, pb["row_axes"], pb["col_axes"], reuse=lu)
     assert lu2 == lu
-    pack.solve(lu, drhs, dsol)
+    pack.solve(lu, [drhs], [1.0], dsol)
     dev.sync()
     ref2 = npp.PencilLU(Mo, Lo, a, 0.11, nf, nx, ny, kx, ky, pb["row_axes"], pb["col_axes"]).solve(rhs)
     assert rel(dev.to_host(dsol), ref2.reshape(sol.shape)) < 1e-11

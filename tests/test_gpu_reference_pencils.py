@@ -98,7 +98,7 @@ def test_every_sweep_variant_at_full_size(full_size_unpaired, full_size, variant
 
 
 def test_fused_rhs_combination_matches_materialised_rhs(full_size):
-    """ddh_pencil_solve_lincomb (RHS formed inside the forward sweep) == lincomb kernel + ddh_pencil_solve, at the
+    """ddh_pencil_solve with several terms (RHS formed inside the forward sweep) == lincomb kernel + one-term solve, at the
     benchmark size, for the 4-term combination of the second RK222 stage"""
     solver, f, ref = full_size
     ts = solver.timestepper
@@ -108,8 +108,8 @@ def test_fused_rhs_combination_matches_materialised_rhs(full_size):
     ex = solver.ex
     rhs, y1, y2 = (ex.empty((solver.R, solver.nx, solver.ny)) for _ in range(3))
     ex.lincomb(rhs, xs, al)
-    solver.pack.solve(lu, rhs, y1)
-    solver.pack.solve_lincomb(lu, xs, al, y2)
+    solver.pack.solve(lu, [rhs], [1.0], y1)
+    solver.pack.solve(lu, xs, al, y2)
     ex.sync()
     assert rel(ex.download(y2), ex.download(y1)) < 1e-14
 

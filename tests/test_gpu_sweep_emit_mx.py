@@ -1,5 +1,5 @@
-"""GPU: M.X written by the backward sweep (solve_backward_kernel<..., EMIT_MX>, ddh_pencil_solve_recombined_tiled_mx) against
-the parent path, the same solve followed by ddh_pencil_matvec_update_tiled on the stored solution.
+"""GPU: M.X written by the backward sweep (solve_backward_kernel<..., EMIT_MX>, ddh_pencil_solve_req::mx_out) against
+the parent path, the same solve followed by a DDH_MATVEC_TILED product on the stored solution.
 
 The solution must be bit-identical.  M.X is summed in another order (the band of M P on y instead of M on x = P y), so both
 paths are measured against a numpy.longdouble product from the same term list: the sweep's maximum error may be at most
