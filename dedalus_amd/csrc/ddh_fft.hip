@@ -1508,6 +1508,25 @@ int ddh_rfft_fused_plan_info(int n_grid, int n_coeff, long nlines, int *info) {
     return 0;
 }
 
+int ddh_fft_plan_info(ddh_handle plan, int mode, long outer, long inner, int second, int deriv, int dvec, int *info) {
+    FftPlan *pl = (FftPlan *)lookup_handle(plan, H_FFT);
+    if (!pl) return -1;
+    if (!info) return fail("ddh_fft_plan_info: null pointer");
+    // FftMode pairs (forward, backward) in the order of FftKind
+    if (mode < RFFT_FWD || mode > CFFT_BWD || mode / 2 != pl->tkind)
+        return fail("ddh_fft_plan_info: mode is not one of the plan's transform kind");
+    if (outer < 1 || inner < 1) return fail("ddh_fft_plan_info: outer >= 1, inner >= 1");
+    const TransformPlan tp = transform_plan(pl->dev, mode, outer, inner, second != 0, deriv != 0, dvec != 0, false);
+    if (tp.error) return fail(tp.error);
+    info[0] = tp.kernel == TransformKernel::cheb_wave ? 0 : tp.kernel == TransformKernel::rfft_wave ? 1
+              : tp.kernel == TransformKernel::cheb_contig_wave ? 2 : 3;
+    info[1] = tp.wave() ? 0 : tp.B;
+    info[2] = (int)tp.block;
+    info[3] = (int)tp.grid;
+    info[4] = (int)tp.lds;
+    return 0;
+}
+
 int ddh_plan_mmt(ddh_handle *plan, int n_out, int n_in, const double *mat_h) {
     if (n_out < 1 || n_in < 1) return fail("plan_mmt: sizes must be positive");
     MmtPlan *pl = new MmtPlan();

@@ -495,7 +495,8 @@ TransformPlan transform_plan(const FftDev &d, int mode, long outer, long inner, 
     }
     while (B > 1 && per_line * B > 64 * 1024) B /= 2;
     if ((long)B > tp.npairs) B = (int)tp.npairs;
-    if (per_line * B > 160 * 1024) {
+    // the launch's whole dynamic-LDS request (lines and the two-level twiddle table) against the 160 KiB of a workgroup
+    if (per_line * B + (size_t)tw_entries(N) * sizeof(double2) > 160 * 1024) {
         tp.error = "transform: axis too long for the LDS kernel";
         return tp;
     }

@@ -122,6 +122,7 @@ SIGNATURES = {
     "ddh_fft_set_stage_window": [_h, _i, _i],
     "ddh_fft_wave_launches": [C.POINTER(_l)],
     "ddh_fft_wave_size": [_i, _i, _i, _ip],
+    "ddh_fft_plan_info": [_h, _i, _l, _l, _i, _i, _i, _ip],
     "ddh_cheb_backward": [_h, _vp, _vp, _l, _l, _vp],
     "ddh_plan_mmt": [_hp, _i, _i, _dp],
     "ddh_mmt_apply": [_h, _vp, _vp, _l, _l, _vp],

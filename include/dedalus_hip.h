@@ -147,6 +147,15 @@ int ddh_fft_wave_launches(long *count);
  * array layouts only the wave kernels read (ddh_fft_set_stage_layout, ddh_cheb_forward_tiled) ask this instead of keeping
  * a copy of the tables.                                                                                               */
 int ddh_fft_wave_size(int kind, int n_grid, int n_coeff, int *covered);
+/* ... and the launch one transform call on `plan` would make, as the entry points decide it (nothing is launched or
+ * allocated).  mode: 0 / 1 real Fourier forward / backward, 2 / 3 Chebyshev, 4 / 5 complex Fourier, of the plan's kind;
+ * outer, inner: the call's; second: a dual entry point (two outputs); deriv: ddh_rfft_backward_deriv; dvec: the dual
+ * Chebyshev entry point's derivative vector is given.  info[5]:
+ *   [0] kernel: 0 strided Chebyshev wave, 1 strided real-Fourier wave, 2 contiguous Chebyshev wave, 3 workgroup-per-tile
+ *   [1] line pairs (complex: lines) per workgroup of the workgroup kernel (0 for the wave kernels)
+ *   [2] threads per workgroup   [3] workgroups   [4] dynamic LDS bytes
+ * A shape no kernel takes is the error the transform call itself would return.                                        */
+int ddh_fft_plan_info(ddh_handle plan, int mode, long outer, long inner, int second, int deriv, int dvec, int *info);
 int ddh_cheb_backward(ddh_handle plan, const double *c, double *g, long outer, long inner, void *stream);
 
 /* Dense matrix-multiply transform along an axis (JacobiMMT core/transforms.py:114-158 via
