@@ -10,11 +10,13 @@ import numbers
 import numpy as np
 
 from .curvioperand import NonlinearError
+from .packbase import PackBase
 from .problems import _split_equation
 
 
-class MatvecPack:
-    """matvec interface the shared timesteppers use (pack.matvec(id, x, y)) over device term lists"""
+class MatvecPack(PackBase):
+    """matvec interface the shared timesteppers use (pack.matvec(id, x, y)) over device term lists; no capability
+    of core/packbase.py beyond that"""
 
     def __init__(self):
         self.mats = []

@@ -20,6 +20,7 @@ from . import timesteppers as ts_mod
 from .evaluator import Evaluator, SystemBuffer, _full_sep
 from .field import Field
 from .ivp_common import IVPLifecycle
+from .packbase import PackBase, PreContractPack
 from .polyop import flatten
 from .problems import LinCtx
 
@@ -30,6 +31,15 @@ logger = logging.getLogger(__name__)
 class SolverBase:
     def __init__(self, problem, **kw):
         self.problem = problem
+        self.modal = None                   # the matrix-free modal solve of a triply periodic box (_build_modal), else None
+        self.solve_probe = None             # parity probe (tests, bench.py `parity`): dict(groups=..., records=[...])
+        self.allow_block_inverse = False    # (initial-value solvers: many solves per factorization)
+        self.factor_calls = 0               # factorizations of the pack (none with the modal solve)
+        self._lu_params = {}                # factorization id -> (a, b)
+        self._binv = None                   # explicit block inverses: None not planned yet, False off, else the plan's dict
+        self._memo = {}                     # answers decided once per solver (rhs_tiling of the problem, device masks)
+        self._overlap_work = None           # state-only work a timestepper hands the next evaluate_F (overlaps_rhs_work)
+        self._last_rhs = None               # the last materialised right-hand side (parity tests)
         self.dist = dist = problem.dist
         self.ex = dist.executor
         self.variables = list(problem.variables)
@@ -90,7 +100,8 @@ class SolverBase:
         self.L_tl = self._assemble("L")
         self._make_invalid_modes_inert()
         self._decouple_boundary_rows()
-        self.pack = self.ex.make_pack(nf, self.R, nx, ny, kx, ky, dist._mx_offset)
+        pack = self.ex.make_pack(nf, self.R, nx, ny, kx, ky, dist._mx_offset)
+        self.pack = pack if isinstance(pack, PackBase) else PreContractPack(pack)   # (an executor older than the contract)
         self.M_id = self.pack.add_matrix(self.M_tl)
         self.L_id = self.pack.add_matrix(self.L_tl)
         self._build_recombination()
@@ -158,8 +169,6 @@ class SolverBase:
         """The matrix-free modal solve (core/modal.py, csrc/ddh_modal.hip) for a problem with a Fourier pencil axis on an
         executor that has it; otherwise -- more than 8 component rows, the executors of the tests, DDH_MODAL=0 -- the
         band LU over the pencil, whose bandwidth is about twice the number of component rows."""
-        self.modal = None
-        self._modal_lus = []
         if not getattr(self.dist, "_pencil_fourier", None):
             return
         reason = "DDH_MODAL=0"
@@ -178,9 +187,8 @@ class SolverBase:
 
     def factor_bytes(self):
         """Device memory held by the factorizations of the implicit systems (0 for the matrix-free modal solve)."""
-        if self.modal is not None:
-            return 0
-        return sum(int(self.pack.lu_bytes(lu)) for lu in getattr(self, "_lu_params", {}))
+        backend = self.modal or self.pack
+        return sum(int(backend.lu_bytes(lu)) for lu in self._lu_params)
 
     # ---- assembly ----------------------------------------------------------------------------------------
     def _flags(self, domain):
@@ -440,7 +448,7 @@ class SolverBase:
                 cols = [c for k in range(nc) for c in cols if lc[c] == k]
                 self.n_blocks = nc
                 self.block_sizes = [int(np.sum(lr == k)) for k in range(nc)]
-                if len(set(self.block_sizes)) == 1 and hasattr(self.pack, "set_row_blocks"):
+                if len(set(self.block_sizes)) == 1 and self.pack.supports_row_blocks:
                     self.pack.set_row_blocks(nc)      # (sweeps with one thread per (system, block))
         self.n_interior = len(rows)
         rows += flat(eq_sp)
@@ -480,7 +488,7 @@ class SolverBase:
         (ddh_pencil_set_pairing): half the factorizations, half the factor stream of every solve.  Verified here on the
         term lists of (a M + b L) P and of P; any mismatch leaves pairing off."""
         self.pairing = None
-        if not hasattr(self.pack, "set_pairing") or os.environ.get("DDH_PAIR", "1") == "0":
+        if not self.pack.supports_pairing or os.environ.get("DDH_PAIR", "1") == "0":
             return
         if self.nf != 2 or self.real_grading is None or self.dist.size > 1:
             return
@@ -753,7 +761,7 @@ class SolverBase:
         whose address the allocator may hand out again after unrelated data lived there -- is zeroed on every call."""
         ev, ex = self.evaluator_core, self.ex
         ev.new_pass()
-        work = self.__dict__.pop("_overlap_work", None) or []    # (state-only work of the caller: overlaps_rhs_work)
+        work, self._overlap_work = self._overlap_work or [], None    # (state-only work of the caller: overlaps_rhs_work)
         if self._grid_windows() == 1:
             for f in work:
                 f()
@@ -912,7 +920,7 @@ class SolverBase:
         sy = 1 if (self.nf < 2 or v.domain.by_axis[sep[1]] is None) else self.ny
         if sx == 1 and self.nf >= 1 and self.dist._mx_offset != 0:
             return          # data without x dependence belongs to the kx = 0 pencils of the first rank
-        if getattr(self, "x_banded", 0):            # (sx = sy = 1, _state_tiling_ok: entry (row, 0, 0) of a kx-band-major state)
+        if self.x_banded:                           # (sx = sy = 1, _state_tiling_ok: entry (row, 0, 0) of a kx-band-major state)
             xs = self.X.as_strided((info["rows"], 1, 1), (8 * self.ny, 1, 1), self.X.storage_offset() + info["row0"] * 8 * self.ny)
         else:
             xs = self.X[info["row0"]:info["row0"] + info["rows"]].reshape(info["rows"], self.nx, self.ny)[:, :sx, :sy]
@@ -937,7 +945,7 @@ class SolverBase:
     # ---- tile-major state vector ---------------------------------------------------------------------------
     def _state_tiling_ok(self):
         ex = self.ex
-        if os.environ.get("DDH_X_TILED", "1") == "0" or not hasattr(ex, "tile_rows") or not hasattr(self.pack, "set_state_tiled"):
+        if os.environ.get("DDH_X_TILED", "1") == "0" or not hasattr(ex, "tile_rows") or not self.pack.supports_state_tiling:
             return False
         if self.nf != 2 or self.nx % 8 or self.ny % 8 or self.dist.size > 1:
             return False
@@ -1010,19 +1018,19 @@ class SolverBase:
         product -- properties of the problem, decided once -- and the lean forward sweep over real factors for EVERY
         factorization in `lus` (an id or an iterable of ids), asked again on every call: the sweep variant belongs to a
         factorization and to PencilPack.set_solve_variant, not to the solver.  DDH_NO_RHS_TILING=1 switches it off (A/B)."""
-        if getattr(self, "_rhs_tiling_problem", None) is None:
-            self._rhs_tiling_problem = self._rhs_tiling_of_problem()
-        if not self._rhs_tiling_problem:
+        if "rhs_tiling" not in self._memo:
+            self._memo["rhs_tiling"] = self._rhs_tiling_of_problem()
+        if not self._memo["rhs_tiling"]:
             return 0
         for lu in ([lus] if isinstance(lus, (int, np.integer)) else list(lus)):
             info = self.pack.lu_info(lu)
             if info["forward"] != "lean" or not info["real"]:
                 return 0
-        return self._rhs_tiling_problem
+        return self._memo["rhs_tiling"]
 
     def _rhs_tiling_of_problem(self):
         ex = self.ex
-        if (os.environ.get("DDH_NO_RHS_TILING") is not None or not getattr(self.pack, "supports_tiled_rhs", False)
+        if (os.environ.get("DDH_NO_RHS_TILING") is not None or not self.pack.supports_tiled_rhs
                 or self.nf != 2 or self.nx % 8 or self.ny % 8 or self.F_direct is None or self.P_id is None
                 or self.real_grading is None or self.nx * self.ny < int(os.environ.get("DDH_RHS_TILING_MIN", 4 * 16384))
                 or not hasattr(ex, "tiled_forward_ok")):
@@ -1050,12 +1058,11 @@ class SolverBase:
 
     def solve(self, lu, rhs, out):
         """out = (a M + b L)^-1 rhs  through the recombined band factorization: X = P Y."""
-        if getattr(self, "modal", None) is not None:
-            a, b = self._modal_lus[lu]
-            self.modal.solve(a, b, [rhs], [1.0], out)
+        if self.modal is not None:
+            self.modal.solve_factored(lu, [rhs], [1.0], out)
         else:
             self._pack_solve(lu, [rhs], [1.0], out)
-        if getattr(self, "solve_probe", None) is not None:
+        if self.solve_probe is not None:
             # (this label is recorded as it always was, whatever the pack and with or without P: deliberately not the
             #  one `_pack_solve` returns from `solve_path_label`)
             self._probe_record(lu, rhs, out, path="ddh_pencil_solve_recombined (one materialised right-hand side)")
@@ -1063,18 +1070,16 @@ class SolverBase:
     def _pack_solve(self, lu, xs, alphas, out, zero_rows=None, skip_rows=None, tiled=False, mx_out=None):
         """The one call of the pack behind `solve` and `solve_lincomb`; returns the label of the feature set it used."""
         Y = out if self.P_id is None else self.ex.empty((self.R, self.nx, self.ny))
-        if not getattr(self.pack, "solves_requests", False):
-            # the oracle's pack keeps the reference's steps apart (oracle/np_executor.py): axpy chain, solve, P mat-vec
-            self.pack.solve_lincomb(lu, xs, alphas, Y)
-            if self.P_id is not None:
-                self.pack.matvec(self.P_id, Y, out)
-            return solve_path_label(False)
         if self.P_id is None:
             self.pack.solve(lu, xs, alphas, out)
             return solve_path_label(False)
         self.pack.solve(lu, xs, alphas, out, p_mat_id=self.P_id, work=Y, zero_rows=zero_rows, skip_rows=skip_rows, tiled=tiled,
                         mx=None if mx_out is None else (self.M_id, mx_out))
-        return solve_path_label(True, zero_rows is not None or skip_rows is not None, tiled, mx_out is not None)
+        # (the "recombined" labels name the kernels that take masks, tile-major terms and M.X with P; a pack with none of
+        #  these keeps P a mat-vec after the solve and its label says so, as it always did)
+        pk = self.pack
+        fused_p = pk.supports_zero_rows or pk.supports_tiled_rhs or pk.supports_mx_emission
+        return solve_path_label(fused_p, zero_rows is not None or skip_rows is not None, tiled, mx_out is not None)
 
     def _probe_record(self, lu, rhs, out, path, skip_rows=None, terms=1, zero_rows=None):
         """Parity probe (tests, bench.py `parity`): the right-hand side and the solution of the solve that just ran, on the
@@ -1082,8 +1087,8 @@ class SolverBase:
         not store -- their entries of `x` are stale by design and the record says which."""
         probe = self.solve_probe
         a, b = self._lu_params[lu]
-        if getattr(self, "x_tiled", 0):
-            out = self.untile_rows(out, banded=bool(getattr(self, "x_banded", 0)))  # (every solution vector of such a pack)
+        if self.x_tiled:
+            out = self.untile_rows(out, banded=bool(self.x_banded))  # (every solution vector of such a pack)
         rec = dict(a=a, b=b, path=path, terms=int(terms), zero_rows=bool(zero_rows), skip_rows=skip_rows is not None,
                    rhs=[self.gather_pencil(rhs, "equations", gx, gy) for gx, gy in probe["groups"]],
                    x=[self.gather_pencil(out, "variables", gx, gy) for gx, gy in probe["groups"]])
@@ -1131,32 +1136,23 @@ class SolverBase:
         """Device form (byte mask, fraction set) of `zero_rows_host`, or None.  A Runge-Kutta right-hand side built from M.X
         and F vectors only (timesteppers.RungeKuttaIMEX) passes it to the solve, whose forward sweep then does not read
         those rows (ddh_pencil_solve_req::zero_rows)."""
-        if getattr(self, "_zrows", "unset") != "unset":
-            return self._zrows
-        self._zrows = None
-        if not getattr(self.pack, "supports_zero_rows", False) or self.P_id is None:
-            return None
-        if os.environ.get("DDH_NO_ZERO_ROWS") is not None:
-            return None
-        mask = self.zero_rows_host()
-        if mask is not None and mask.any():
-            self._zrows = self._device_mask(mask)
-        return self._zrows
+        if "zero_rows" not in self._memo:
+            mask = None
+            if self.pack.supports_zero_rows and self.P_id is not None and os.environ.get("DDH_NO_ZERO_ROWS") is None:
+                mask = self.zero_rows_host()
+            self._memo["zero_rows"] = self._device_mask(mask) if mask is not None and mask.any() else None
+        return self._memo["zero_rows"]
 
     def intermediate_skip_rows(self):
         """Device form of `skip_rows_host`, or None: the solve of an INTERMEDIATE Runge-Kutta stage does not store these
         unknowns (they are final only after the last stage)."""
-        if getattr(self, "_skiprows", "unset") != "unset":
-            return self._skiprows
-        self._skiprows = None
-        if not getattr(self.pack, "supports_zero_rows", False) or self.P_id is None or self.F_direct is None:
-            return None
-        if os.environ.get("DDH_NO_SKIP_ROWS") is not None:
-            return None
-        mask = self.skip_rows_host()
-        if mask.any():
-            self._skiprows = self._device_mask(mask)
-        return self._skiprows
+        if "skip_rows" not in self._memo:
+            mask = None
+            if (self.pack.supports_zero_rows and self.P_id is not None and self.F_direct is not None
+                    and os.environ.get("DDH_NO_SKIP_ROWS") is None):
+                mask = self.skip_rows_host()
+            self._memo["skip_rows"] = self._device_mask(mask) if mask is not None and mask.any() else None
+        return self._memo["skip_rows"]
 
     MX_WINDOW = 18          # y_j .. y_(j+17): the register window of the backward sweep that emits M.X (csrc/ddh_pencil.hip MXW)
 
@@ -1177,7 +1173,7 @@ class SolverBase:
     def prepare_mx_emission(self, lu):
         """Whether the sweeps of factorization `lu` can write M.X (PencilPack.emits_mx) and the analysis of M P allows it;
         hands the tables of `mx_band_tables` to the factorization when both hold."""
-        if not getattr(self.pack, "supports_mx_emission", False) or self.P_id is None or getattr(self, "modal", None) is not None:
+        if not self.pack.supports_mx_emission or self.P_id is None or self.modal is not None:
             return False
         if not self.pack.emits_mx(lu, self.P_id):
             return False
@@ -1192,7 +1188,7 @@ class SolverBase:
         """Whether the timestepper lets the tiled solves of EVERY factorization in `lus` write M.X of their solution from the
         backward sweep (`prepare_mx_emission`): one rank, a tile-major state; asked again after every refactorization and
         change of the sweep variant, like `rhs_tiling`."""
-        if self.dist.size > 1 or not getattr(self, "x_tiled", 0):
+        if self.dist.size > 1 or not self.x_tiled:
             return False
         return all(self.prepare_mx_emission(lu) for lu in lus)
 
@@ -1202,25 +1198,17 @@ class SolverBase:
         mx_out (tiled solves where `sweep_emits_mx` holds): the backward sweep also writes M.out there."""
         if mx_out is not None and not (tiled and self.P_id is not None and len(xs) <= self.pack.MAX_RHS_TERMS):
             raise RuntimeError("M.X from the sweep needs the tiled fused recombined solve")
-        probe = getattr(self, "solve_probe", None)
-        if getattr(self, "modal", None) is not None and probe is None and len(xs) <= self.modal.MAX_RHS_TERMS and not tiled:
-            a, b = self._modal_lus[lu]
-            self.modal.solve(a, b, xs, alphas, out)         # (the combination is formed while the cells are loaded)
-            return
-        if getattr(self, "modal", None) is not None:
-            if tiled:
-                raise RuntimeError("tile-major right-hand sides need the fused recombined solve")
-            rhs = self.ex.empty((self.R, self.nx, self.ny))
-            self.ex.lincomb(rhs, xs, alphas)
-            self._last_rhs = rhs
-            return self.solve(lu, rhs, out)
-        if tiled and (self.P_id is None or not getattr(self.pack, "solves_requests", False) or len(xs) > self.pack.MAX_RHS_TERMS):
+        probe, backend = self.solve_probe, self.modal or self.pack
+        fits = len(xs) <= backend.MAX_RHS_TERMS
+        if tiled and (backend is not self.pack or self.P_id is None or not self.pack.supports_tiled_rhs or not fits):
             raise RuntimeError("tile-major right-hand sides need the fused recombined solve")
-        if len(xs) > self.pack.MAX_RHS_TERMS:
+        if not fits or (backend is self.modal and probe is not None):
             rhs = self.ex.empty((self.R, self.nx, self.ny))
             self.ex.lincomb(rhs, xs, alphas)
             self._last_rhs = rhs                       # (kept for the parity tests)
             return self.solve(lu, rhs, out)
+        if backend is self.modal:
+            return self.modal.solve_factored(lu, xs, alphas, out)    # (the combination is formed while the cells are loaded)
         rhs_rec = None
         if probe is not None:
             # The probe must certify the kernels that are TIMED: the same fused call runs below, with the same terms and
@@ -1244,7 +1232,7 @@ class SolverBase:
             # stores them -- poison them and a consumer shows up as NaN in the end state (tests/test_gpu_ivp.py)
             t = self.ex.torch
             idx = t.nonzero(skip_rows[0]).flatten()
-            if getattr(self, "x_banded", 0):
+            if self.x_banded:
                 out.reshape(self.nx // 8, self.R, -1)[:, idx] = float("nan")
             else:
                 out.reshape(self.R, -1)[idx] = float("nan")
@@ -1295,22 +1283,14 @@ class SolverBase:
         return np.concatenate(parts)
 
     def factor(self, a, b, reuse=-1):
-        if getattr(self, "modal", None) is not None:
-            # nothing to factor: the id names the pair (a, b) the modal solve assembles its systems with
-            if reuse >= 0:
-                lu = reuse
-                self._modal_lus[lu] = (float(a), float(b))
-            else:
-                lu = len(self._modal_lus)
-                self._modal_lus.append((float(a), float(b)))
-            self.__dict__.setdefault("_lu_params", {})[lu] = (float(a), float(b))
+        if self.modal is not None:
+            lu = self.modal.factor(a, b, reuse=reuse)       # (nothing is factored: the id names the pair)
+            self._lu_params[lu] = (float(a), float(b))
             return lu
-        self.factor_calls = getattr(self, "factor_calls", 0) + 1
+        self.factor_calls += 1
         lu = self.pack.factor(self.MP_id, self.LP_id, a, b, self.row_perm, self.col_perm, self.n_interior,
                               self.kl, self.ku, self.row_axes, self.col_axes, reuse=reuse,
                               real=self.real_grading)
-        if not hasattr(self, "_lu_params"):
-            self._lu_params = {}
         self._lu_params[lu] = (float(a), float(b))
         self._block_inverses(lu, a, b)
         return lu
@@ -1325,15 +1305,15 @@ class SolverBase:
     # the GEMV streams.  Same systems as the reference's per-subproblem LU (libraries/matsolvers.py:126-149).
     def _block_inverse_plan(self, any_executor=False):
         """any_executor: the host analysis alone (tests)"""
-        if getattr(self, "_binv", None) is not None:
+        if self._binv is not None:
             return self._binv
         self._binv = False
         rg, n = self.real_grading, self.n_interior
-        if not getattr(self, "allow_block_inverse", False):      # (initial-value solvers: many solves per factorization)
+        if not self.allow_block_inverse:
             return False
         if os.environ.get("DDH_BLOCK_INVERSE", "1") == "0" or self.nf != 1 or rg is None or getattr(self.dist, "size", 1) > 1 or n < 128:
             return False
-        if not any_executor and (getattr(self.ex, "name", "") != "hip" or not hasattr(self.pack, "set_block_inverse")):
+        if not any_executor and (getattr(self.ex, "name", "") != "hip" or not self.pack.supports_block_inverse):
             return False
         ns = self.n_blocks if (self.n_blocks > 1 and len(set(self.block_sizes)) == 1 and os.environ.get("DDH_SPLIT_THREADS", "1") != "0") else 1
         nh = n // ns
@@ -1388,7 +1368,7 @@ class SolverBase:
     def _drop_block_inverses(self, bi=None):
         """Every registered explicit inverse is withdrawn from the library BEFORE its device memory is released (the
         pack holds caller-owned pointers): the sweeps of the kept LU take over."""
-        bi = bi if isinstance(bi, dict) else getattr(self, "_binv", None)
+        bi = bi if isinstance(bi, dict) else self._binv
         if isinstance(bi, dict):
             for k in list(bi["x"]):
                 self.pack.set_block_inverse(k, None)
@@ -1406,7 +1386,7 @@ class SolverBase:
             self._drop_block_inverses(bi)
             self._binv = False
             return
-        flagged = sorted(getattr(self.pack, "flagged", {}).get(lu, []))
+        flagged = sorted(self.pack.flagged.get(lu, []))
         nb = self.R - self.n_interior
         if nb:
             # Border (gauge) unknowns exist for the k = 0 pencil only (checked by the plan): blockinv_solve_kernel ignores
@@ -1712,12 +1692,13 @@ class LinearBoundaryValueSolver(SolverBase):
     """L.X = F in one batched factor + solve (core/solvers.py LBVP role)."""
 
     _lu = None
+    _F_lbvp = None
 
     def solve(self, rebuild_matrices=False):
         """The LHS does not change between calls: it is factored once (the reference factors at build time,
         core/solvers.py:393-406) and re-factored into the same device storage only on request."""
         self.sync_state_to_device()
-        if getattr(self, "_F_lbvp", None) is None:
+        if self._F_lbvp is None:
             self._F_lbvp = self.ex.empty((self.R, self.nx, self.ny))        # owned by the solver, reused by every solve
         F = self._F_lbvp
         self.evaluate_F(F)

@@ -347,6 +347,10 @@ class RungeKuttaIMEX(_SolveMixin):
         # M.X of the state from the backward sweep of the solve that wrote it (SolverBase.sweep_emits_mx): the iteration
         # whose start state the last stage's sweep left in MX0, or None
         self._mx0_iteration = None
+        # the layout of the M.X and F buffers and who writes M.X, decided in step() for a set of factorizations and a sweep
+        # variant (`_tiled_stamp`); None: not decided yet
+        self._tiled = self._tiled_stamp = None
+        self._emit = False
 
     def step(self, dt, wall_time=None):
         s = self.solver
@@ -368,17 +372,17 @@ class RungeKuttaIMEX(_SolveMixin):
         # (asked BEFORE the synchronisation, which uploads a host edit and leaves the state looking untouched)
         state_kept = bool(getattr(s, "_state_is_clean", lambda: False)())
         s.sync_state_to_device()
-        own = dict(owned=True) if getattr(pack, "supports_zero_rows", False) else {}
+        own = dict(owned=True) if pack.supports_zero_rows else {}
         # the M.X and F buffers of this timestepper in the tile-major layout the sweeps read contiguously
         # (SolverBase.rhs_tiling).  The answer belongs to the current factorizations and sweep variant: asked again after
         # every refactorization and every PencilPack.set_solve_variant.  Every buffer is rewritten in every step, so a
         # change of layout only has to restore the zeros of the rows nothing writes.
-        stamp = (tuple(self._lus.values()), getattr(pack, "variant_epoch", 0))
-        if getattr(self, "_tiled_stamp", None) != stamp:
+        stamp = (tuple(self._lus.values()), pack.variant_epoch)
+        if self._tiled_stamp != stamp:
             tiled_now = 0
             if own and not self._direct and not any(v is not None for v in self.LX) and hasattr(s, "rhs_tiling"):
                 tiled_now = s.rhs_tiling(self._lus.values())
-            if getattr(self, "_tiled", None) is not None and bool(tiled_now) != bool(self._tiled):
+            if self._tiled is not None and bool(tiled_now) != bool(self._tiled):
                 for buf in [self.MX0] + self.F + [v for v in self.MX if v is not None]:
                     ex.fill_zero(buf)
                 s._F_zeroed = set(b.data_ptr() if hasattr(b, "data_ptr") else id(b) for b in self.F)

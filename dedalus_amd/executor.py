@@ -772,6 +772,7 @@ class ModalSolve:
 
     def __init__(self, ex, plan):
         self.ex, self.plan = ex, plan
+        self._ab = []                   # "factorization" id -> (a, b)
         u8 = lambda a: np.ascontiguousarray(a, dtype=np.uint8)
         i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
         f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
@@ -786,6 +787,21 @@ class ModalSolve:
                     int(plan.nrows_x), libhip.as_ip(rr), libhip.as_ip(xr), libhip.as_ubp(ax), int(ti.size), libhip.as_ip(ti),
                     libhip.as_ip(tj), libhip.as_dp(cre), libhip.as_dp(cim), libhip.as_ubp(exs), libhip.as_ubp(eys),
                     libhip.as_ubp(ezs), libhip.as_ubp(fl))
+
+    def factor(self, a, b, reuse=-1):
+        """Nothing is factored: the id names the pair (a, b) `solve` assembles its systems with (reuse: that id again)."""
+        if reuse < 0:
+            self._ab.append(None)
+            reuse = len(self._ab) - 1
+        self._ab[reuse] = (float(a), float(b))
+        return reuse
+
+    def lu_bytes(self, lu):
+        return 0
+
+    def solve_factored(self, lu, xs, alphas, x):
+        """`solve` with the pair (a, b) that `factor` named lu"""
+        return self.solve(*self._ab[lu], xs, alphas, x)
 
     def solve(self, a, b, xs, alphas, x, rhs_tiled=False, x_tiled=False):
         """x = (a M + b L)^-1 sum_t alphas[t] xs[t]"""

@@ -12,6 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import libhip
+from .core.packbase import PackBase
 from .device import ptr
 
 
@@ -62,7 +63,16 @@ class TermList:
         return A
 
 
-class PencilPack:
+class PencilPack(PackBase):
+    # the whole contract of core/packbase.py: one `solve` takes the terms, P, the masks and M.x in one request
+    supports_tiled_rhs = True
+    supports_zero_rows = True
+    supports_mx_emission = True
+    supports_pairing = True
+    supports_row_blocks = True
+    supports_state_tiling = True
+    supports_block_inverse = True
+
     def __init__(self, dev, nfourier, nrows, nx, ny, kx, ky, mx_offset=0):
         self.dev = dev
         self.mx_offset = int(mx_offset)
@@ -79,6 +89,12 @@ class PencilPack:
         self.matrices = []
         self.lu_meta = {}
         self.executor = None
+        self.flagged = {}               # lu id -> flagged cells
+        self.state_tiled = 0
+        self.variant_epoch = 0
+        self._flag_dinv = {}            # inverses of the flagged pencils, by matrices, ordering and cells
+        self._flag_dense = False        # the bordered-band form of those inverses met a zero pivot: dense from then on
+        self._binv_bytes = {}           # lu id -> bytes of its explicit block inverses
 
     def add_matrix(self, tl):
         row = np.ascontiguousarray(tl.row)
@@ -94,7 +110,7 @@ class PencilPack:
         return mid.value
 
     def _timer(self):
-        return getattr(self.executor, "timer", None) if self.executor is not None else None
+        return self.executor.timer if self.executor is not None else None
 
     def matvec(self, mat_id, x, y, owned=False, tiled=False):
         """y = A x.  owned: y is a zero-initialised buffer that only this product writes (a timestepper's M.X vector): rows
@@ -108,13 +124,6 @@ class PencilPack:
     def _matvec(self, mat_id, x, y, owned=False, tiled=False):
         flags = libhip.MATVEC_TILED if tiled else (libhip.MATVEC_OWNED if owned else 0)
         libhip.call("ddh_pencil_matvec", self.handle, mat_id, ptr(x), ptr(y), flags, self.dev.stream)
-
-    # what core/solvers.py asks a pack before it chooses a path; the oracle's pack (oracle/np_executor.py) declares none of
-    # them and is driven step by step
-    supports_tiled_rhs = True
-    supports_zero_rows = True
-    solves_requests = True          # `solve` takes the terms, P, the masks and M.x in one request
-    supports_mx_emission = True     # `emits_mx` / `set_mx_band` / solve(..., mx=)
 
     def set_state_tiled(self, on):
         """The vector every solve of this pack writes and every mat-vec of it reads (the solver's state X) is tile-major
@@ -169,7 +178,6 @@ class PencilPack:
         libhip.call("ddh_pencil_flagged", self.handle, lu_id, C.byref(count),
                     cells.ctypes.data_as(C.POINTER(C.c_long)), cells.size)
         nflag = count.value
-        self.flagged = {} if not hasattr(self, "flagged") else self.flagged
         self.flagged[lu_id] = [int(c) for c in cells[:min(nflag, cells.size)]]
         if nflag > cells.size or nflag * self.S * self.nrows ** 2 * 16 > 8e9:
             raise libhip.DdhError("%d pencils have a singular band block: problem structure unsupported by the "
@@ -211,7 +219,7 @@ class PencilPack:
         if n_interior is None:
             n_interior = N
         key = (matM, matL, row_perm.tobytes(), col_perm.tobytes(), tuple(int(c) for c in cells))
-        cache = self.__dict__.setdefault("_flag_dinv", {})
+        cache = self._flag_dinv
         if key not in cache:
             M, L = self.matrices[matM], self.matrices[matL]
             Ms, Ls, rvs, cvs, slots = [], [], [], [], []
@@ -237,7 +245,7 @@ class PencilPack:
             if not cx:
                 Ms, Ls = [m.real.copy() for m in Ms], [m.real.copy() for m in Ls]
             band = None
-            if (not cx and os.environ.get("DDH_FLAG_DENSE", "0") != "1" and not getattr(self, "_flag_dense", False)
+            if (not cx and os.environ.get("DDH_FLAG_DENSE", "0") != "1" and not self._flag_dense
                     and all(rv.all() and cv.all() for rv, cv in zip(rvs, cvs))):
                 band = [self._bordered_band(Md, Ld, n_interior) for Md, Ld in zip(Ms, Ls)]
                 if any(bd is None for bd in band):
@@ -275,7 +283,7 @@ class PencilPack:
         """explicit transposed inverses [cell][block][k][i] of the diagonal blocks (device array, kept alive by the caller),
         or None: a `solve` with p_mat_id then applies them instead of running the sweeps"""
         libhip.call("ddh_pencil_set_block_inverse", self.handle, int(lu_id), ptr(binv) if binv is not None else None)
-        self.__dict__.setdefault("_binv_bytes", {})[int(lu_id)] = int(binv.numel()) * 8 if binv is not None else 0
+        self._binv_bytes[int(lu_id)] = int(binv.numel()) * 8 if binv is not None else 0
 
     def solve(self, lu_id, xs, alphas, x, p_mat_id=None, work=None, zero_rows=None, skip_rows=None, tiled=False, mx=None):
         """x = (a M + b L)^-1 (sum_t alphas[t] xs[t]), the combination formed inside the forward sweep; with p_mat_id,
@@ -303,7 +311,7 @@ class PencilPack:
             wrote = 1.0 - (skip_rows[1] if skip_rows is not None else 0.0)
             mrows = len(np.unique(np.asarray(self.matrices[mx[0]].row)))
             return self.lu_bytes(lu_id) + (terms * read + x.numel() * wrote + mx[1].numel() * mrows / float(self.nrows)) * 8
-        binv = getattr(self, "_binv_bytes", {}).get(lu_id)
+        binv = self._binv_bytes.get(lu_id)
         if binv:                            # explicit block inverses: they are what the solve streams, not the factors
             return binv + (terms + 3 * x.numel()) * 8      # (+ work written, read by the P mat-vec, x written)
         wrote = 1.0 - (skip_rows[1] if (skip_rows is not None and info["backward_lanes"] == 0 and info["real"]) else 0.0)
@@ -325,13 +333,11 @@ class PencilPack:
         q.m_mat_id, q.mx_out = (-1, None) if mx is None else (int(mx[0]), mx[1].data_ptr())
         libhip.call("ddh_pencil_solve", self.handle, lu_id, C.byref(q), self.dev.stream)
 
-    MAX_RHS_TERMS = 8
-
     def set_solve_variant(self, mode=1, fwd=-1, backward_lanes=-1):
         """Sweep variant of solve(): mode 1 by the number of systems (default), 0 one thread per system, 2 cooperative;
         fwd (0 / 1) and backward_lanes (0 / 4 / 16) override the two sweeps individually."""
         libhip.call("ddh_pencil_set_solve_variant", self.handle, int(mode), int(fwd), int(backward_lanes))
-        self.variant_epoch = getattr(self, "variant_epoch", 0) + 1     # (layout decisions that depend on the variant: timesteppers)
+        self.variant_epoch += 1         # (layout decisions that depend on the variant: timesteppers)
 
     def set_pairing(self, row_swap, col_swap, min_systems=0):
         """Partner pencils (ddh_pencil_set_pairing): (my, mx) is solved with the factorization of (mx, my) through the

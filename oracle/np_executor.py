@@ -10,11 +10,16 @@ and as the parity oracle / CPU baseline; the product never selects it by itself.
 
 import numpy as np
 
+from dedalus_amd.core.packbase import PackBase
+
 from . import np_pencil as npp
 from . import np_transforms as npt
 
 
-class _NpPack:
+class _NpPack(PackBase):
+    """The pack contract (dedalus_amd/core/packbase.py) over the reference's per-pencil loops: terms and P only."""
+    supports_pairing = True
+
     def __init__(self, nf, nrows, nx, ny, kx, ky, mx_offset=0):
         self.mx_offset = mx_offset
         self.nf, self.nrows, self.nx, self.ny = nf, nrows, nx, ny
@@ -22,6 +27,8 @@ class _NpPack:
         self.mats = []
         self.lus = []
         self.lu_meta = {}
+        self.posts = []
+        self.pairing = None
 
     def set_pairing(self, row_swap, col_swap, min_systems=0):
         """The x <-> y symmetry the solver found (dedalus_amd/core/solvers.py _build_pairing).  The oracle keeps one
@@ -40,7 +47,6 @@ class _NpPack:
         from scipy import sparse
         bands = np.asarray(bands, float).reshape(len(offsets), nz)
         C = sparse.diags([bands[d, :nz - o] for d, o in enumerate(offsets)], list(offsets), shape=(nz, nz)).tocsr()
-        self.posts = getattr(self, "posts", [])
         self.posts.append((nz, C))
         return len(self.posts) - 1
 
@@ -63,20 +69,26 @@ class _NpPack:
         self.lus.append(lu)
         return len(self.lus) - 1
 
-    def solve(self, lu_id, rhs, x):
-        x[...] = self.lus[lu_id].solve(rhs).reshape(x.shape)
-
-    MAX_RHS_TERMS = 8
-
-    def solve_lincomb(self, lu_id, xs, alphas, x):
-        """axpy chain into the RHS buffer, then the per-pencil solves (timesteppers.py:617-623, 641-643)"""
-        rhs = np.zeros_like(x)
+    def solve(self, lu_id, xs, alphas, x, p_mat_id=None, work=None, zero_rows=None, skip_rows=None, tiled=False, mx=None):
+        """The request of the pack contract with the reference's steps kept apart: the axpy chain into a zeroed RHS buffer
+        (timesteppers.py:617-623, 641-643), the per-pencil solves, and with p_mat_id the mat-vec x = P work."""
+        if tiled:
+            raise ValueError("the oracle pack takes no tile-major terms")
+        if mx is not None:
+            raise ValueError("the oracle pack does not write M.x")
+        if zero_rows is not None:
+            raise ValueError("the oracle pack takes no zero_rows mask")
+        if skip_rows is not None:
+            raise ValueError("the oracle pack takes no skip_rows mask")
+        if p_mat_id is not None and work is None:
+            raise ValueError("the oracle pack applies P through a work vector")
+        y = x if p_mat_id is None else work
+        rhs = np.zeros_like(y)
         for v, a in zip(xs, alphas):
-            rhs += a * np.asarray(v).reshape(x.shape)
-        self.solve(lu_id, rhs, x)
-
-    def lu_bytes(self, lu_id):
-        return 0
+            rhs += a * np.asarray(v).reshape(y.shape)
+        y[...] = self.lus[lu_id].solve(rhs).reshape(y.shape)
+        if p_mat_id is not None:
+            self.matvec(p_mat_id, work, x)
 
 
 class NumpyExecutor:

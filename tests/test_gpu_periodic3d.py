@@ -137,3 +137,41 @@ def test_repeated_runs_and_graph_replay_are_bit_identical():
     for k in runs[0]:
         assert np.array_equal(runs[0][k], runs[1][k]), k
         assert np.array_equal(runs[0][k], runs[2][k]), k
+
+
+def test_solve_lincomb_term_counts_and_probe_on_the_modal_solve():
+    """SolverBase.solve_lincomb on the modal solve at 12 x 20 x 8: 1 and 8 terms go to the kernel as they are, 9 terms (more
+    than it takes) and a probed call through one materialised right-hand side.  Same right-hand side, same solution, and a
+    modal launch every time."""
+    import dedalus_amd.public as d3
+    from test_periodic3d import TOL
+    solver, f = pc.taylor_green(d3, (12, 20, 8), "RK222")
+    assert solver.modal is not None and solver.modal.MAX_RHS_TERMS == 8
+    ex, shape = solver.ex, (solver.R, solver.nx, solver.ny)
+    lu = solver.factor(1.0, 0.5 * pc.DT)
+    rhs = np.random.default_rng(11).normal(size=shape)
+    parts = [ex.from_host(rhs * w) for w in (0.5, 0.25, 0.125, 0.0625, 0.03125, 0.015625, 0.0078125, 0.00390625, 0.00390625)]
+    whole = ex.from_host(rhs)
+
+    def run(xs, alphas):
+        out, n0 = ex.zeros(shape), modal_launches()
+        solver.solve_lincomb(lu, xs, alphas, out)
+        ex.sync()
+        assert modal_launches() > n0
+        return np.array(ex.download(out))
+
+    x1 = run([whole], [1.0])
+    x8 = run(parts[:7] + [parts[7]], [1.0] * 7 + [2.0])
+    x9 = run(parts, [1.0] * 9)
+    solver.solve_probe = dict(groups=pc.MATRIX_GROUPS, records=[])
+    xp = run(parts[:7] + [parts[7]], [1.0] * 7 + [2.0])
+    recs, solver.solve_probe = solver.solve_probe["records"], None
+    assert [r["path"] for r in recs] == ["ddh_pencil_solve_recombined (one materialised right-hand side)"]
+    assert recs[0]["terms"] == 1 and (recs[0]["a"], recs[0]["b"]) == (1.0, 0.5 * pc.DT)
+    assert solver.factor_calls == 0 and solver.factor_bytes() == 0
+    scale = np.abs(x1).max()
+    assert scale > 0 and np.isfinite(x1).all()
+    for name, x in (("8 terms", x8), ("9 terms", x9), ("probed", xp)):
+        err = np.abs(x - x1).max() / scale
+        print("%s: %.2e" % (name, err))
+        assert err <= TOL, (name, err)
